@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — G1 MSM throughput at 2^20 bases per GPU (BASELINE.json configs[1]), plus the Tate-pairing rate (configs[2]) and Groth16
 proofs/s at 2^20 constraints (configs[3]) on MI355X.  Contract: python bench.py --gpus N --steps K --warmup W (N>1 under
-torch.distributed.run, one rank per GPU).  One JSON line on rank 0.
+torch.distributed.run, one rank per GPU).  One JSON line on rank 0.  --dump-outputs DIR also writes the result of the last timed step
+(seeded inputs: the same arguments give the same inputs on every run, so two builds can be compared output for output).
 
 step  = one MSM over 2^20 device-resident bases (a CRS) and 2^20 device-resident 255-bit scalars, result normalised to an affine
         point on the host.
@@ -12,7 +13,6 @@ value = total scalar-muls per second over all ranks (terms / wall time, max over
 Beside it for N>1: `strong` (ONE 2^20-term MSM cut N ways) and `groth16` both sharded (one proof over N GPUs) and as replicas
 (N keys, N independent proofs in flight) — the honest multi-GPU picture, not only the embarrassingly parallel one."""
 import argparse, ctypes, importlib, json, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # the MSM pipeline wants its three stage streams on distinct hardware queues
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -48,6 +48,15 @@ def rand_scalars_mod_r(seed, n):
     return np.ascontiguousarray(out[:n])
 
 
+def dump_outputs(d, point):
+    """--dump-outputs: the affine point (zkt_g1_affine, include/zkt.h) a caller of the timed MSM receives, as 25 float64 values: the 32-bit words
+    of x[6] and y[6], least significant first, then is_infinity (the padding word is left out).  Each word is exact in float64."""
+    p = np.ascontiguousarray(point, dtype=np.uint64).reshape(13)
+    words = np.concatenate([p[:12].view(np.uint32), (p[12:13] & np.uint64(0xFFFFFFFF)).astype(np.uint32)])
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "g1_msm_last_step.npy"), words.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -62,7 +71,10 @@ def main():
     ap.add_argument("--no-bulletproofs", dest="bulletproofs", action="store_false", help="skip the Bulletproofs leg (BASELINE config 5)")
     ap.add_argument("--scalar-dist", default="uniform", choices=["uniform", "ones", "bits"],
                     help="uniform in [0,r) (the metric) | all ones | random 0/1 (skew stress: one hot bucket)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the result of the last timed MSM to DIR/g1_msm_last_step.npy (float64; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -216,6 +228,8 @@ def main():
         zk.check(L.zkt_g1_msm_dev(h, vp(d_scalars), n, sp, outp, None))
         latency_ms = (time.perf_counter() - t0) * 1e3
     elapsed, kern_ms = timed(h, (d_scalars, d_scalars_b), n, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)      # `out` holds what the last timed step collected
     ms_per_step = elapsed / args.steps * 1e3
     value = world * n * args.steps / elapsed
     k_ms = float(np.mean(kern_ms))

@@ -1,4 +1,4 @@
-"""diagnostic: the inversion entry points one by one (run under rocgdb when one of them takes the process down)"""
+"""diagnostic: the inversion entry points one by one (each name is printed before its call, so the last name printed is the one that took the process down)"""
 import ctypes, importlib, sys, os
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
