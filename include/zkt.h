@@ -318,7 +318,7 @@ int zkt_bp_inner_product_argument_ctx(zkt_bp_ipa_ctx* ctx, const zkt_secp_affine
  * alpha, rho, y, z, tau1, tau2, x, sL[n], sR[n] (the values the reference draws at :76,:79-81,:84-85,:97-98,:102);
  * u = the random point of :137 and xs the inner-product challenges (only with use_ipa).  out_pts (optional) = A,S,T1,T2,P.
  * The context built for gg, hh, u (window-multiple table, work buffers: ~20 ms at 65,536 generators) is kept after the call and reused by the next
- * one-shot call that brings the same generators byte for byte (host pointers; ZKT_BP_CTX_CACHE=0 disables); zkt_bp_inner_product_argument likewise. */
+ * one-shot call that brings the same generators byte for byte (host pointers); zkt_bp_inner_product_argument likewise. */
 int zkt_bp_range_proof(size_t n, const zkt_secp_affine* V, const uint64_t* aL, const uint64_t* gamma, const zkt_secp_affine* g,
                        const zkt_secp_affine* h, const zkt_secp_affine* gg, const zkt_secp_affine* hh, int use_ipa,
                        const uint64_t* rnd, const zkt_secp_affine* u, const uint64_t* xs, zkt_secp_affine* out_pts);

@@ -1,10 +1,7 @@
-"""The affine pair-tree rounds ahead of the G2 bucket accumulation (zk-toolkit_amd/csrc/zkt_msm_affine.hip; Polynomial::eval_with_g2_hidings,
-polynomial.rs:283-293, summed with the reference's own affine addition macros.rs:34-163 and one shared inversion per lane).  Measured inside the product they lose
-to the lane-pair XYZZ kernel (profiles/r04_batched_affine_go_no_go.md), so they are OFF by default and kept as a tested alternative: the resident-base tests below
-run in this process on the default plan, and once more in a child process with the rounds FORCED for every resident G2 sum (ZKT_G2_AFFINE_ROUNDS=2,
-ZKT_G2_AFFINE_MIN_ENTRIES=1) — same oracle, every exceptional case of the addition (repeated bases: the tangent; a base and its negative: infinity; a base at
-infinity) inside the rounds.  (All of 1, 2 and 3 rounds passed when the path was brought up; one child keeps the suite short.)"""
-import ctypes, importlib, os, subprocess, sys
+"""Resident G2 MSMs (Polynomial::eval_with_g2_hidings, polynomial.rs:283-293) on the default plan against the oracle's sequential sum (the reference's own
+affine addition, macros.rs:34-163): small sizes with zero, one and out-of-range scalars, and pools of exceptional cases for the bucket accumulation — repeated
+bases (the tangent), a base and its negative (infinity), bases at infinity, and buckets that hold almost every term."""
+import ctypes, importlib
 import numpy as np
 import pytest
 from zkt_testlib import *
@@ -62,7 +59,7 @@ def test_resident_g2_msm_vs_oracle(L, n):
 @pytest.mark.parametrize("kind", ["pool", "ones", "bits", "same-point"])
 def test_resident_g2_msm_exceptional_cases(L, kind):
     """Equal points in one bucket (P + P: the tangent, macros.rs:57-108), opposite points (P + (-P) = infinity, macros.rs:53-56), bases at infinity, and buckets that hold
-    almost everything (all scalars one / 0-1: the carry-free digit puts every term of a window into one bucket) — inside the affine rounds when they are forced."""
+    almost everything (all scalars one / 0-1: the carry-free digit puts every term of a window into one bucket)."""
     n = 300
     rng = SplitMix64(8800)
     g = np.zeros((1, G2W), np.uint64); O.zkto_g2_generator(ptr(g))
@@ -84,17 +81,3 @@ def test_resident_g2_msm_exceptional_cases(L, kind):
         ss = [1] * n if kind == "ones" else [rng.below(2) for _ in range(n)]
     sc = ints_to_arr(ss, 4)
     assert (_resident_msm(L, bases, sc) == _oracle_sum(bases, sc)).all()
-
-
-@pytest.mark.parametrize("rounds", [2])
-def test_affine_rounds_forced_in_a_child_process(rounds):
-    """Every resident G2 sum of the child takes `rounds` affine rounds: the tests of this file, the eight-slot pipeline, the sharded partials and the G2 leg of the
-    Groth16 / Pinocchio provers (whose B sums are resident G2 sets) against the same oracle."""
-    if os.environ.get("ZKT_G2_AFFINE_MIN_ENTRIES"): pytest.skip("already inside the forced child")
-    env = dict(os.environ, ZKT_G2_AFFINE_MIN_ENTRIES="1", ZKT_G2_AFFINE_ROUNDS=str(rounds))
-    here = os.path.dirname(os.path.abspath(__file__))
-    sel = ("resident_g2_msm or (msm_eight_slots_in_flight and g2) or (sharded_msm_partials_combine and g2) or (r1cs_path_matches_reference_algorithm and (chain16 or bits61 or cubic))"
-           " or pinocchio_resident_prover")
-    r = subprocess.run([sys.executable, "-m", "pytest", here, "-m", "gpu", "-x", "-q", "-k", sel, "-p", "no:cacheprovider"], env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout

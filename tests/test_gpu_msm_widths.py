@@ -15,8 +15,7 @@ def test_resident_msm_parity_at_a_forced_window_width(width):
     here = os.path.dirname(os.path.abspath(__file__))
     sel = ("((resident_g2_msm or msm_eight_slots_in_flight or sharded_msm_partials_combine or msm_vs_oracle) and not config)"
            " or (r1cs_path_matches_reference_algorithm and (chain16 or cubic)) or pinocchio_resident_prover")
-    r = subprocess.run([sys.executable, "-m", "pytest", here, "-m", "gpu", "-x", "-q", "-k", sel, "-p", "no:cacheprovider", "--deselect", os.path.join(here, "test_gpu_msm_widths.py"),
-                        "--deselect", os.path.join(here, "test_gpu_msm_affine.py") + "::test_affine_rounds_forced_in_a_child_process"],
+    r = subprocess.run([sys.executable, "-m", "pytest", here, "-m", "gpu", "-x", "-q", "-k", sel, "-p", "no:cacheprovider", "--deselect", os.path.join(here, "test_gpu_msm_widths.py")],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout

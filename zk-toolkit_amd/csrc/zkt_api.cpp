@@ -720,26 +720,12 @@ static int jac_sum_dev(int grp, const uint32_t* dev_partials, size_t count, void
   if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
   return zkt_internal_jac_sum(grp, dev_partials, count, 3 * grp_coord_bytes(grp) / 4, (hipStream_t)stream, out);
 }
-// one-shot host-pointer MSM: upload, build the window-multiple table, run, free
 // one-shot host-pointer MSM (eval_with_g1_hidings called once, polynomial.rs:271-281): the table-free form — upload, kernel layout,
 // sort / accumulate / per-window reduce / join on one stream, free.  No window-multiple table is built for a single use.
-// ZKT_MSM_ONE_SHOT_TABLE=1 selects the resident-bases machinery instead (A/B and regression checks).
 static int msm_host(int grp, const void* bases, const uint64_t* scalars, size_t n, void* out) {
   if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
   if (!out || (n && (!bases || !scalars)) || n >= (size_t(1) << 26)) return ZKT_ERR_SHAPE;      // entry offsets are 32-bit: nwin * n < 2^32
   if (n == 0) { memset(out, 0, grp_pt_bytes(grp)); ((uint32_t*)out)[grp_pt_bytes(grp) / 4 - 2] = 1; return ZKT_OK; }
-  static const bool use_table = [] { const char* e = getenv("ZKT_MSM_ONE_SHOT_TABLE"); return e && *e == '1'; }();
-  if (use_table) {
-    zkt_bases_impl* h = nullptr;
-    int rc = bases_upload(grp, bases, n, &h);
-    if (rc) return rc;
-    uint64_t* d_s = nullptr;
-    if (hipMalloc((void**)&d_s, n * 32) != hipSuccess) { bases_free(h); return ZKT_ERR_DEVICE; }
-    hipMemcpy(d_s, scalars, n * 32, hipMemcpyHostToDevice);
-    rc = msm_dev(h, d_s, n, g.stream, out, nullptr);
-    hipFree(d_s); bases_free(h);
-    return rc;
-  }
   const MsmPlan plan = msm_plan_direct(n, grp);
   const size_t ptb = grp_pt_bytes(grp), cb = grp_coord_bytes(grp);
   uint8_t* blob = nullptr;                                   // [abi points | scalars | kernel-layout points | inf flags | jac | abi out | workspace]

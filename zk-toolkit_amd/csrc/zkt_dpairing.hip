@@ -524,10 +524,9 @@ __device__ __attribute__((noinline)) Fq d_final_exp_3h(const Ctx& c, const Fq& f
   return d_mul(c, a, d_mul(c, d_cyc_sqr(c, g), g));             // * g^3
 }
 
-// f_{r-1,P}(untwist(Q)) up to Fq6 factors for the group's pair, as miller_g1_g2 (pairing.h); in_g1 <- r P == infinity.
-// SHORT: f_{x^2,P} over the 127 bits of x^2 as miller_g1_g2_short — the callers have Q's membership of G2 and the curve equations checked by
-// k_short_loop_guards beside this kernel, and redo what fails them.
-template <bool SHORT> __device__ __attribute__((noinline)) Fq d_miller(const Ctx& c, const Aff<FqOps>& p, const Aff<Fq2Ops>& q, bool& in_g1) {
+// f_{x^2,P}(untwist(Q)) up to Fq6 factors for the group's pair over the 127 bits of x^2, as miller_g1_g2_short (pairing.h); in_g1 <- r P == infinity.
+// The callers have Q's membership of G2 and the curve equations checked by k_short_loop_guards beside this kernel, and redo what fails them.
+__device__ __attribute__((noinline)) Fq d_miller(const Ctx& c, const Aff<FqOps>& p, const Aff<Fq2Ops>& q, bool& in_g1) {
   {   // slot file: every lane computes the same values, the group's first lane stores them
     const Fq2 xi_inv = xi_inv_const();
     const Fq2 Xq = fq2_mul(q.x, xi_inv), Yq = fq2_mul(q.y, xi_inv);
@@ -540,57 +539,28 @@ template <bool SHORT> __device__ __attribute__((noinline)) Fq d_miller(const Ctx
   }
   Fq f = d_one(c);
 #pragma unroll 1
-  for (int i = 0; i < (SHORT ? MILLER_X2_NBITS : MILLER_NAF_DIGITS); ++i) {
-    uint32_t nz = 0, ng = 0;
-    if constexpr (SHORT) {
+  for (int i = 0; i < MILLER_X2_NBITS; ++i) {
+    uint32_t nz = 0;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) nz = (j == (i >> 5)) ? miller_x2_bits_word(j) : nz;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { nz = (j == (i >> 5)) ? miller_naf_nz_word(j) : nz; ng = (j == (i >> 5)) ? miller_naf_neg_word(j) : ng; }
-    }
-    const bool bit = (nz >> (i & 31)) & 1, neg = (ng >> (i & 31)) & 1;
+    for (int j = 0; j < 4; ++j) nz = (j == (i >> 5)) ? miller_x2_bits_word(j) : nz;
+    const bool bit = (nz >> (i & 31)) & 1;
     f = d_sqr(c, f);
     point_dbl(c);
     f = d_mul_line(c, f);
-    if (bit) { point_add(c, neg); f = d_mul_line(c, f); }
+    if (bit) { point_add(c, false); f = d_mul_line(c, f); }
   }
-  // r P == infinity?  V = (r-1) P must equal -P;  after the short loop V = x^2 P must equal (BETA xp, -yp)  (miller_pt_is_x2, pairing.h)
+  // r P == infinity?  After the loop V = x^2 P must equal (BETA xp, -yp)  (miller_pt_is_x2, pairing.h)
   const Fq X = slotv(c, P_X), Y = slotv(c, P_Y), Z = slotv(c, P_Z);
   const Fq ZZ = fp_sqr(Z);
-  const Fq xw = SHORT ? fp_mul(g1_beta_const(), p.x) : p.x;
+  const Fq xw = fp_mul(g1_beta_const(), p.x);
   in_g1 = !fp_is_zero(Z) && fp_eq(fp_mul(xw, ZZ), X) && fp_eq(fp_mul(fp_mul(p.y, ZZ), Z), fp_neg(Y));
   return f;
-}
-
-// one Tate pairing per group.  Marks elements whose P is outside G1 for k_tate_exact_marked, exactly as k_tate does.
-template <bool SHORT> __global__ void __launch_bounds__(64) k_dtate(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ g2, uint32_t* __restrict__ out, size_t n,
-                                              unsigned long long* err, uint32_t mark_word, uint32_t mark) {
-  __shared__ uint32_t lds[LDS_WORDS];
-  const Ctx c = make_ctx(lds);
-  const int lane = threadIdx.x;
-  size_t e = (size_t)blockIdx.x * GPW + (lane / GL < GPW ? lane / GL : GPW - 1);
-  const bool live = e < n && lane < GPW * GL;
-  if (e >= n) e = n - 1;
-  Aff<FqOps> p = PtIO<FqOps>::ld(g1 + e * ABI_G1_WORDS);
-  Aff<Fq2Ops> q = PtIO<Fq2Ops>::ld(g2 + e * ABI_G2_WORDS);
-  const bool inf = p.inf || q.inf;
-  if (inf) {                                   // RationalFunction::new_* / eval_with_* panic on infinity: report, then run on dummy data to keep the barriers uniform
-    if (live) atomicMin(err, (unsigned long long)e);
-    p.x = fp_one<FqC>(); p.y = fp_one<FqC>(); q.x = fq2_one(); q.y = fq2_one();
-  }
-  bool in_g1;
-  const Fq f = d_miller<SHORT>(c, p, q, in_g1);
-  const Fq r = d_final_exp<SHORT>(c, f);
-  if (!live || inf) return;
-  if (!in_g1) { if (c.r.g == 0) out[e * 144 + mark_word] = mark; return; }
-  st_fp<FqC>(out + e * 144 + abi_word(c.r.m, c.r.part), r);
 }
 
 // prod_k tate(+-P_k, Q_k) == target (or == 1) per element, K <= 4 pairs: the K Miller loops run side by side in K groups of one wave,
 // the group results meet in the first group's LDS image, ONE final exponentiation follows.  Same contract as k_pairing_product_check /
 // k_groth16_verify (zkt_pairing.hip): infinity -> error index, a G1 argument outside the order-r subgroup -> ok = 0.
-template <int K, bool SHORT>
+template <int K>
 __global__ void __launch_bounds__(64) k_dproduct(PairArgs a, const uint32_t* __restrict__ target, uint32_t* __restrict__ ok, size_t n, unsigned long long* err,
                                                  const uint8_t* __restrict__ kcount) {
   __shared__ uint32_t lds[LDS_WORDS];
@@ -610,7 +580,7 @@ __global__ void __launch_bounds__(64) k_dproduct(PairArgs a, const uint32_t* __r
   if (inf) { p.x = fp_one<FqC>(); p.y = fp_one<FqC>(); q.x = fq2_one(); q.y = fq2_one(); }
   if (a.neg[pair]) p.y = fp_neg(p.y);
   bool in_g1;
-  Fq f = d_miller<SHORT>(c, p, q, in_g1);
+  Fq f = d_miller(c, p, q, in_g1);
   // kcount (optional): element e multiplies only its first kcount[e] pairs.  The caller fills the unused slots with a copy of pair 0, so everything up to
   // here ran on valid points; the spare group hands over one and raises no flag (Pinocchio's 2-pair and 3-pair equalities in ONE launch of K = 3).
   if (kcount && pair >= (int)kcount[e]) { f = d_one(c); in_g1 = true; inf = false; }
@@ -626,8 +596,8 @@ __global__ void __launch_bounds__(64) k_dproduct(PairArgs a, const uint32_t* __r
     const Fq prod = dot_mul(c.img(0), lead + 1 * IMG_SLOTS * SW, c.r.m, c.r.part);
     f = (pair == 0) ? prod : f;                                   // groups k > 0 keep their own value until it has been handed over
   }
-  // SHORT: (prod tate)^(1/(2x^2-1)) is one exactly when the Tate product is; against a target the corrected exponentiation gives the product itself
-  const Fq r = (SHORT && target) ? d_final_exp<true>(c, f) : d_final_exp<false>(c, f);
+  // (prod tate)^(1/(2x^2-1)) is one exactly when the Tate product is; against a target the corrected exponentiation gives the product itself
+  const Fq r = target ? d_final_exp<true>(c, f) : d_final_exp<false>(c, f);
   uint32_t w[12]; fp_to_words(r, w);
   uint32_t diff = 0;
   const int off = abi_word(c.r.m, c.r.part);
@@ -872,11 +842,36 @@ __global__ void __launch_bounds__(64) k_key_ab(const uint32_t* __restrict__ alph
     if (threadIdx.x == 0) atomicOr(flag, bit);
   } else {
     bool in_g1;
-    const Fq f = d_miller<true>(c, p, q, in_g1);
+    const Fq f = d_miller(c, p, q, in_g1);
     const Fq r = d_final_exp<true>(c, f);
     if (inf || !in_g1 || threadIdx.x >= GL) return;
     st_fp<FqC>(gt + abi_word(c.r.m, c.r.part), r);
   }
+}
+// one Tate pairing per group (the 127-step loop).  Marks elements whose P is outside G1 for k_tate_exact_marked, exactly as k_tate does.
+// Defined last on purpose: the kernels' order in the module decides the frames of the shared noinline helpers.  Defined ahead of k_dproduct, it left
+// k_dtate and k_dproduct<3> with 192 B more scratch per lane and k_key_ab with 28 more VGPRs.
+__global__ void __launch_bounds__(64) k_dtate(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ g2, uint32_t* __restrict__ out, size_t n,
+                                              unsigned long long* err, uint32_t mark_word, uint32_t mark) {
+  __shared__ uint32_t lds[LDS_WORDS];
+  const Ctx c = make_ctx(lds);
+  const int lane = threadIdx.x;
+  size_t e = (size_t)blockIdx.x * GPW + (lane / GL < GPW ? lane / GL : GPW - 1);
+  const bool live = e < n && lane < GPW * GL;
+  if (e >= n) e = n - 1;
+  Aff<FqOps> p = PtIO<FqOps>::ld(g1 + e * ABI_G1_WORDS);
+  Aff<Fq2Ops> q = PtIO<Fq2Ops>::ld(g2 + e * ABI_G2_WORDS);
+  const bool inf = p.inf || q.inf;
+  if (inf) {                                   // RationalFunction::new_* / eval_with_* panic on infinity: report, then run on dummy data to keep the barriers uniform
+    if (live) atomicMin(err, (unsigned long long)e);
+    p.x = fp_one<FqC>(); p.y = fp_one<FqC>(); q.x = fq2_one(); q.y = fq2_one();
+  }
+  bool in_g1;
+  const Fq f = d_miller(c, p, q, in_g1);
+  const Fq r = d_final_exp<true>(c, f);
+  if (!live || inf) return;
+  if (!in_g1) { if (c.r.g == 0) out[e * 144 + mark_word] = mark; return; }
+  st_fp<FqC>(out + e * 144 + abi_word(c.r.m, c.r.part), r);
 }
 }  // namespace dp
 
@@ -886,19 +881,10 @@ hipError_t launch_dfq12_op(int op, const uint32_t* a, const uint32_t* b, uint32_
   return hipGetLastError();
 }
 
-hipError_t launch_dproduct(const PairArgs& a, int K, const uint32_t* target, uint32_t* ok, size_t n, unsigned long long* err, bool short_loop, hipStream_t s, const uint8_t* kcount) {
+hipError_t launch_dproduct(const PairArgs& a, int K, const uint32_t* target, uint32_t* ok, size_t n, unsigned long long* err, hipStream_t s, const uint8_t* kcount) {
   if (n == 0) return hipSuccess;
-  auto blocks = [&](int epb) { return dim3((unsigned)((n + epb - 1) / epb)); };
-#define ZKT_DPRODUCT(KK, EPB) if (short_loop) hipLaunchKernelGGL((dp::k_dproduct<KK, true>), blocks(EPB), dim3(64), 0, s, a, target, ok, n, err, kcount); \
-                             else hipLaunchKernelGGL((dp::k_dproduct<KK, false>), blocks(EPB), dim3(64), 0, s, a, target, ok, n, err, kcount)
-  switch (K) {
-    case 1: ZKT_DPRODUCT(1, 5); break;
-    case 2: ZKT_DPRODUCT(2, 2); break;
-    case 3: ZKT_DPRODUCT(3, 1); break;
-    case 4: ZKT_DPRODUCT(4, 1); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef ZKT_DPRODUCT
+  if (K != 3) return hipErrorInvalidValue;          // the one caller: launch_groth16_verify_small
+  hipLaunchKernelGGL((dp::k_dproduct<3>), dim3((unsigned)n), dim3(64), 0, s, a, target, ok, n, err, kcount);
   return hipGetLastError();
 }
 hipError_t launch_key_ab(const uint32_t* alpha, const uint32_t* beta, uint32_t* out, uint32_t* flag, uint32_t bit, uint32_t* gt, hipStream_t s) {
@@ -917,10 +903,9 @@ hipError_t launch_dproduct_ate(const PairArgs& a, int K, const uint32_t* target,
   }
   return hipGetLastError();
 }
-hipError_t launch_dtate(const uint32_t* g1, const uint32_t* g2, uint32_t* out, size_t n, unsigned long long* err, uint32_t mark_word, uint32_t mark, bool short_loop, hipStream_t s) {
+hipError_t launch_dtate(const uint32_t* g1, const uint32_t* g2, uint32_t* out, size_t n, unsigned long long* err, uint32_t mark_word, uint32_t mark, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  if (short_loop) hipLaunchKernelGGL(dp::k_dtate<true>, dim3((unsigned)((n + dp::GPW - 1) / dp::GPW)), dim3(64), 0, s, g1, g2, out, n, err, mark_word, mark);
-  else hipLaunchKernelGGL(dp::k_dtate<false>, dim3((unsigned)((n + dp::GPW - 1) / dp::GPW)), dim3(64), 0, s, g1, g2, out, n, err, mark_word, mark);
+  hipLaunchKernelGGL(dp::k_dtate, dim3((unsigned)((n + dp::GPW - 1) / dp::GPW)), dim3(64), 0, s, g1, g2, out, n, err, mark_word, mark);
   return hipGetLastError();
 }
 

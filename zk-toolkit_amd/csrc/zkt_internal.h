@@ -93,15 +93,15 @@ hipError_t launch_pairing_product_check(const PairArgs& a, int K, uint32_t* ok, 
 // lane-distributed pairing (zkt_dpairing.hip): diagnostic Fq12 ops on the distributed form
 hipError_t launch_dfq12_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n, hipStream_t s);
 // one pairing per 12 lanes; elements whose P is outside G1 get out[i*144 + mark_word] = mark (see zkt_tate.hip)
-hipError_t launch_dtate(const uint32_t* g1, const uint32_t* g2, uint32_t* out, size_t n, unsigned long long* err, uint32_t mark_word, uint32_t mark, bool short_loop, hipStream_t s);
-// prod_k tate(+-P_k, Q_k) == target (NULL: == 1) with the K Miller loops in K lane groups of one wave (small batches)
+hipError_t launch_dtate(const uint32_t* g1, const uint32_t* g2, uint32_t* out, size_t n, unsigned long long* err, uint32_t mark_word, uint32_t mark, hipStream_t s);
+// prod_k tate(+-P_k, Q_k) == target (NULL: == 1) on the 127-step loop with the K Miller loops in K lane groups of one wave (small batches; K = 3 only)
 // kcount (optional, device): element i multiplies only its first kcount[i] <= K pairs; its unused slots must hold a copy of its pair 0
-hipError_t launch_dproduct(const PairArgs& a, int K, const uint32_t* target, uint32_t* ok, size_t n, unsigned long long* err, bool short_loop, hipStream_t s, const uint8_t* kcount = nullptr);
+hipError_t launch_dproduct(const PairArgs& a, int K, const uint32_t* target, uint32_t* ok, size_t n, unsigned long long* err, hipStream_t s, const uint8_t* kcount = nullptr);
 // the same decision on the 63-step loop (target: the ate counterpart of a key's alpha_beta, or NULL for == 1); ok = 2 where a Q is outside G2 (left to the kernels behind)
 hipError_t launch_dproduct_ate(const PairArgs& a, int K, const uint32_t* target, uint32_t* ok, size_t n, unsigned long long* err, hipStream_t s, const uint8_t* kcount = nullptr);
 hipError_t launch_key_ab(const uint32_t* alpha, const uint32_t* beta, uint32_t* out, uint32_t* flag, uint32_t bit, uint32_t* gt, hipStream_t s);      // one launch, two lane groups' worth of blocks: a(beta, alpha)^(3h) into out (*flag |= bit when beta is in G2) and tate(alpha, beta) into gt
 hipError_t launch_ate_guards(const PairArgs& a, int K, uint32_t* flags, size_t n, hipStream_t s, uint32_t p_skip = 0);      // flags[i] = 1: every P of element i on E and in G1, every Q on E'
-// Small batches of products with DIFFERENT pair counts in one launch (K = the largest): the 127-step kernels with their guards beside them, as
+// Small batches of products with DIFFERENT pair counts in one launch (K = the largest): the 63-step kernels with their guards beside them, as
 // launch_pairing_product_check does for n*K <= the small-batch limit, but WITHOUT the 255-step / exact re-evaluation: ok[i] = 2 means "element i does not fit
 // the short loop, evaluate it another way".  n * K must be within the small-batch limit.
 hipError_t launch_pairing_product_check_counts(const PairArgs& a, int K, const uint8_t* kcount, uint32_t* ok, size_t n, unsigned long long* err, hipStream_t s);
@@ -127,17 +127,7 @@ struct MsmPlan {
   int direct;          // 1 = table-free one-shot form: `table` is the n bases themselves, every window has its own 2^(c-1) buckets
   size_t half;         // buckets per window, 2^(c-1)
   uint32_t chunk;      // most entries one accumulate task (lane) adds: buckets with more are cut into equal pieces (8..128, pick_chunk)
-  int aff_rounds;      // G2, large resident MSMs: pair-tree rounds in affine coordinates ahead of the XYZZ accumulate (zkt_msm_affine.hip); 0 = none
-  size_t aff_off;      // byte offset of their buffers inside the workspace
 };
-// buffers of the affine rounds (zkt_msm_affine.hip): layer r >= 1 = points + infinity bytes at (offsets[b] >> r) + b; cntR / offR describe the last layer
-struct MsmAffineWs { uint32_t *cntR, *offR, *pref; uint32_t* pts[5]; uint8_t* inf[5]; };
-static constexpr int MSM_AFFINE_MAX_ROUNDS = 4;
-size_t msm_affine_ws_bytes(size_t entries, size_t nbuckets, int rounds, int coord_words);
-MsmAffineWs msm_affine_carve(void* base, size_t entries, size_t nbuckets, int rounds, int coord_words);
-hipError_t launch_msm_affine_final_layer(const uint32_t* offsets, size_t nbuckets, int rounds, const MsmAffineWs& w, hipStream_t s);
-hipError_t launch_msm_affine_rounds_g2(const uint32_t* table, const uint32_t* entries, const uint32_t* offsets, size_t nbuckets, size_t entries_bound, int rounds,
-                                       const MsmAffineWs& w, hipStream_t s);
 MsmPlan msm_plan(size_t n, int grp);
 // table-free form for one-shot calls (zkt_*_msm with host pointers): no window-multiple table to build — nwin bucket sets, the per-window
 // sums reduced side by side (grid.y = window) and joined by nwin-1 runs of c doublings
@@ -161,6 +151,3 @@ hipError_t launch_msm_jac_sum_to_affine(int grp, const uint32_t* jac_partials, s
 // G2 bucket accumulation with two lanes per task (zkt_msm_g2pair.hip, a translation unit with its own namespace): global scope
 hipError_t zkt_launch_accumulate_g2_pair(const uint32_t* table, const uint32_t* entries, const uint32_t* offsets, const void* order, const uint32_t* task_off,
                                          size_t nbuckets, uint32_t* sums, uint32_t* partial, size_t max_tasks, hipStream_t s);
-// DIRECT form behind the affine rounds: bucket b = the points pts[off[b] .. off[b] + cnt[b]) of the last layer (inf[slot] != 0: skip), no entry list, no signs
-hipError_t zkt_launch_accumulate_g2_pair_direct(const uint32_t* pts, const uint8_t* inf, const uint32_t* off, const uint32_t* cnt, const void* order, const uint32_t* task_off,
-                                                size_t nbuckets, uint32_t* sums, uint32_t* partial, size_t max_tasks, hipStream_t s);

@@ -89,14 +89,7 @@ MsmPlan msm_plan(size_t n, int grp) {
   if (c > 20) c = 20;
   p.c = c; p.nwin = (256 + 1 + c - 1) / c; p.nbuckets = size_t(1) << (c - 1);
   size_t ent = (size_t)p.nwin * n;
-  // G2: pair-tree rounds in affine coordinates ahead of the XYZZ accumulate (zkt_msm_affine.hip).  OFF by default: measured inside the product the rounds LOSE to the
-  // lane-pair XYZZ kernel (2^20-term pipelined G2 MSM 8.06 ms without, 8.75 / 9.05 / 9.59 ms with 1 / 2 / 3 rounds; profiles/r04_batched_affine_go_no_go.md) — kept as a
-  // tested alternative behind ZKT_G2_AFFINE_ROUNDS (1..4) and ZKT_G2_AFFINE_MIN_ENTRIES for A/B measurements on other shapes.
-  static const int aff_rounds_cfg = [] { const char* e = getenv("ZKT_G2_AFFINE_ROUNDS"); int r = e ? atoi(e) : 0; return r < 0 ? 0 : r > MSM_AFFINE_MAX_ROUNDS ? MSM_AFFINE_MAX_ROUNDS : r; }();
-  static const size_t aff_min_cfg = [] { const char* e = getenv("ZKT_G2_AFFINE_MIN_ENTRIES"); return e ? (size_t)strtoull(e, nullptr, 10) : (size_t(1) << 22); }();
-  p.aff_rounds = (grp == G_G2 && ent >= aff_min_cfg) ? aff_rounds_cfg : 0;
-  p.aff_off = 0;
-  p.chunk = pick_chunk(ent >> p.aff_rounds, grp);
+  p.chunk = pick_chunk(ent, grp);
   size_t b = 0;
   b += (p.nbuckets + 1) * 4 * 3;          // counts, offsets, cursor
   b += 2 * ent * 4 + 256;                  // entries, slots
@@ -107,7 +100,6 @@ MsmPlan msm_plan(size_t n, int grp) {
   b += 64 * 64 * XYW * 4 + 1024;                                  // block sums of hot buckets (k_merge_hot), hot list
   b += part_ws_bytes(n, p.nbuckets, p.nwin);
   b += 4096;
-  if (p.aff_rounds) { b = (b + 255) & ~(size_t)255; p.aff_off = b; b += msm_affine_ws_bytes(ent, p.nbuckets, p.aff_rounds, coord_words(grp)) + 512; }
   p.ws_bytes = b;
   p.direct = 0; p.half = p.nbuckets;
   return p;
@@ -117,8 +109,6 @@ MsmPlan msm_plan(size_t n, int grp) {
 // left 65,536 one-bucket tasks = ONE wave per SIMD, each lane a serial chain of 32-55 additions at the single-wave multiply-add rate
 // (1.37 ms for an eighth of the work of a 2^20-term MSM, profiles/r02_msm_latency_kernel_trace.txt).
 static uint32_t pick_chunk(size_t entries, int grp) {
-  static const int forced = [] { const char* e = getenv("ZKT_MSM_CHUNK"); return e ? atoi(e) : 0; }();
-  if (forced >= 2 && forced <= (int)MSM_CHUNK_MAX) return (uint32_t)forced;
   // lanes to fill: 256 CUs x 4 SIMDs x 2 waves x 64 lanes (G1, secp256k1), x 1.5 so that the short tail tasks have something to hide under;
   // the G2 pair kernel runs one wave per SIMD and two lanes per task
   const size_t tasks = grp == G_G2 ? (size_t)65536 : (size_t)196608;
@@ -135,7 +125,6 @@ MsmPlan msm_plan_direct(size_t n, int grp) {
   if (c < 9) c = 9;                 // nwin <= 29: k_join_windows folds at most 32 windows in one wave
   if (c > 16) c = 16;
   p.c = c; p.nwin = (256 + 1 + c - 1) / c; p.half = size_t(1) << (c - 1); p.nbuckets = (size_t)p.nwin * p.half; p.direct = 1;
-  p.aff_rounds = 0; p.aff_off = 0;
   size_t ent = (size_t)p.nwin * n;
   p.chunk = pick_chunk(ent, grp);
   size_t b = 0;
@@ -728,8 +717,7 @@ hipError_t PART(launch_msm_sort)(const MsmPlan& P, const uint8_t* inf, const uin
   hipError_t e;
   if ((e = zero_async(w.zero_begin, (uint8_t*)w.zero_end - (uint8_t*)w.zero_begin, s)) != hipSuccess) return e;
   const PartDims pd = part_dims(n, B, P.nwin);
-  static const int force_sort = [] { const char* e = getenv("ZKT_MSM_SORT"); return e ? atoi(e) : 0; }();      // 1: atomics (k_digits), 2: partition sort, 0: by size
-  const bool partition = force_sort == 2 || (force_sort != 1 && (size_t)P.nwin * n >= (size_t(1) << 22));        // below ~2^18 terms the atomics are as fast and take fewer launches
+  const bool partition = (size_t)P.nwin * n >= (size_t(1) << 22);        // below ~2^18 terms the atomics are as fast and take fewer launches
   if (n && partition && pd.P <= PART_MAXP) {
     // large MSMs: the atomic-free two-level partition (k_part_*); the record array lives in the slot buffer
     const uint32_t wb = P.direct ? (uint32_t)P.half : 0u;
@@ -751,29 +739,15 @@ hipError_t PART(launch_msm_sort)(const MsmPlan& P, const uint8_t* inf, const uin
   } else {
     if ((e = zero_async(w.offsets, (B + 1) * 4, s)) != hipSuccess) return e;
   }
-  const uint32_t* task_counts = w.counts;
-  if (P.aff_rounds) {                      // the accumulate kernel sees what the affine rounds leave: ceil(cnt / 2^R) points per bucket
-    const MsmAffineWs aw = msm_affine_carve((uint8_t*)workspace + P.aff_off, (size_t)P.nwin * n, B, P.aff_rounds, coord_words(P.grp));
-    if ((e = launch_msm_affine_final_layer(w.offsets, B, P.aff_rounds, aw, s)) != hipSuccess) return e;
-    task_counts = aw.cntR;
-  }
-  hipLaunchKernelGGL(k_task_count, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, task_counts, B, P.chunk, w.ntask, w.size_hist);
+  hipLaunchKernelGGL(k_task_count, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, w.counts, B, P.chunk, w.ntask, w.size_hist);
   launch_scan(w.ntask, w.task_off, B, w.scan_tmp, s);
-  hipLaunchKernelGGL(k_task_scatter, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, task_counts, B, P.chunk, (const uint32_t*)w.size_hist, w.size_cur, w.order, w.hot);
+  hipLaunchKernelGGL(k_task_scatter, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, w.counts, B, P.chunk, (const uint32_t*)w.size_hist, w.size_cur, w.order, w.hot);
   return hipGetLastError();
 }
 // stage 2 (VALU bound, the dominant kernel): one bucket per lane
 hipError_t PART(launch_msm_accumulate)(const MsmPlan& P, const uint32_t* table, void* workspace, hipStream_t s) {
   MsmWs w = carve(P, workspace);
 #if defined(ZKT_MSM_PART_OTHER) && !defined(ZKT_G2_ONE_LANE)
-  if (P.grp == G_G2 && P.aff_rounds) {      // affine pair-tree rounds, then the XYZZ accumulate over their last layer (zkt_msm_affine.hip)
-    const size_t ent = (size_t)P.nwin * P.n;
-    const MsmAffineWs aw = msm_affine_carve((uint8_t*)workspace + P.aff_off, ent, P.nbuckets, P.aff_rounds, coord_words(P.grp));
-    hipError_t e = launch_msm_affine_rounds_g2(table, (const uint32_t*)w.entries, (const uint32_t*)w.offsets, P.nbuckets, ent, P.aff_rounds, aw, s);
-    if (e != hipSuccess) return e;
-    return ::zkt_launch_accumulate_g2_pair_direct(aw.pts[P.aff_rounds], aw.inf[P.aff_rounds], aw.offR, aw.cntR, (const void*)w.order, (const uint32_t*)w.task_off, P.nbuckets,
-                                                  w.sums, w.partial, w.max_tasks, s);
-  }
   if (P.grp == G_G2)        // two lanes per task: zkt_msm_g2pair.hip
     return ::zkt_launch_accumulate_g2_pair(table, (const uint32_t*)w.entries, (const uint32_t*)w.offsets, (const void*)w.order, (const uint32_t*)w.task_off, P.nbuckets,
                                            w.sums, w.partial, w.max_tasks, s);

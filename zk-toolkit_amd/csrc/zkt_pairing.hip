@@ -63,7 +63,6 @@ __global__ void __launch_bounds__(64) k_ate_guards(PairArgs a, int K, uint32_t* 
   const unsigned long long b = __ballot(bad);
   if (i < n && k == 0) flags[i] = ((b >> (threadIdx.x & ~3)) & 15ull) ? 0u : 1u;
 }
-static bool small_ate() { static const bool on = [] { const char* e = getenv("ZKT_PRODUCT_LOOP"); return !(e && atoi(e) == 127); }(); return on; }
 hipError_t launch_ate_guards(const PairArgs& a, int K, uint32_t* flags, size_t n, hipStream_t s, uint32_t p_skip) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_ate_guards, dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, s, a, K, flags, n, p_skip);
@@ -381,9 +380,9 @@ hipError_t launch_groth16_verify_small(const uint32_t* A, const uint32_t* B, con
   uint32_t* flags = nullptr; hipStream_t side;
   if ((e = hipMallocAsync((void**)&flags, n * sizeof(uint32_t), s)) != hipSuccess) return e;
   // ate_target (the key's ate counterpart of alpha_beta, k_ate_key_prep): the 63-step loop, its guards beside it; otherwise the 127-step loop against alpha_beta itself
-  const bool ate = ate_target && small_ate();
+  const bool ate = ate_target != nullptr;
   if ((e = guard_fork(s, &side)) != hipSuccess || (e = (ate ? launch_ate_guards(a, 3, flags, n, side, 2u) : launch_short_loop_guards(a, 3, flags, n, side))) != hipSuccess ||
-      (e = (ate ? launch_dproduct_ate(a, 3, ate_target, ok, n, err, s) : launch_dproduct(a, 3, alpha_beta, ok, n, err, true, s))) != hipSuccess ||
+      (e = (ate ? launch_dproduct_ate(a, 3, ate_target, ok, n, err, s) : launch_dproduct(a, 3, alpha_beta, ok, n, err, s))) != hipSuccess ||
       (e = guard_join(s, side)) != hipSuccess) { (void)hipFreeAsync(flags, s); return e; }
   hipLaunchKernelGGL(k_product_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint32_t*)flags, ok, n);
   if ((e = hipFreeAsync(flags, s)) != hipSuccess) return e;
@@ -442,11 +441,12 @@ hipError_t launch_groth16_verify(const uint32_t* A, const uint32_t* B, const uin
 // Equality of pairing products as the reference's callers test it (lhs == rhs on GTPoints: signature.rs:34-39,
 // pinocchio/verifier.rs:43-84): e(P1,Q1) == e(P2,Q2) e(P3,Q3)  <=>  tate-product(P1,Q1; -P2,Q2; -P3,Q3) == 1, since
 // e(-P,Q) = e(P,Q)^-1 exactly.  One element per lane; an argument at infinity is the reference's panic (rational_function.rs:36,59).
-template <int K, bool SHORT>
-__global__ void __launch_bounds__(64) k_pairing_product_check(PairArgs a, uint32_t* __restrict__ ok, size_t n, unsigned long long* err, int only_redo) {
+// Elements the 63-step kernels before marked OK_REDO, on the 255-step loop.
+template <int K>
+__global__ void __launch_bounds__(64) k_pairing_product_check(PairArgs a, uint32_t* __restrict__ ok, size_t n, unsigned long long* err) {
   size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (i >= n) return;
-  if (only_redo && ok[i] != OK_REDO) return;
+  if (ok[i] != OK_REDO) return;
   Fq xp[K], yp[K]; Fq2 xq[K], yq[K];
   bool inf = false;
   for (int k = 0; k < K; ++k) {
@@ -456,15 +456,9 @@ __global__ void __launch_bounds__(64) k_pairing_product_check(PairArgs a, uint32
     xp[k] = p.x; yp[k] = a.neg[k] ? fp_neg(p.y) : p.y; xq[k] = q.x; yq[k] = q.y;
   }
   if (inf) { atomicMin(err, (unsigned long long)i); ok[i] = 0; return; }
+  for (int k = 0; k < K; ++k) if (!g1_on_curve(xp[k], yp[k]) || !g2_on_curve(xq[k], yq[k])) { ok[i] = OK_EXACT; return; }
   bool in_g1;
-  Fq12 e;
-  if constexpr (SHORT) {                   // (prod tate)^(1/(2x^2-1)) is one exactly when the Tate product is: no correction needed for "== 1"
-    if (!pairing_args_fit_short_loop<K>(xp, yp, xq, yq)) { ok[i] = OK_REDO; return; }
-    e = final_exponentiation(miller_g1_g2_multi_short<K>(xp, yp, xq, yq, in_g1));
-  } else {
-    for (int k = 0; k < K; ++k) if (!g1_on_curve(xp[k], yp[k]) || !g2_on_curve(xq[k], yq[k])) { ok[i] = OK_EXACT; return; }
-    e = final_exponentiation(miller_g1_g2_multi<K>(xp, yp, xq, yq, in_g1));
-  }
+  const Fq12 e = final_exponentiation(miller_g1_g2_multi<K>(xp, yp, xq, yq, in_g1));
   if (!in_g1) { ok[i] = OK_EXACT; return; }       // as in k_groth16_verify
   uint32_t got[144]; st_fq12(got, e);
   uint32_t diff = got[132] ^ 1u;                       // canonical one: w0.v0.u0 = 1 (the last Fq of the {w1,w0} layout), all else 0
@@ -478,9 +472,8 @@ hipError_t launch_pairing_product_check_counts(const PairArgs& a, int K, const u
   if (K < 1 || K > 4 || !kcount || n * (size_t)K > dproduct_limit()) return hipErrorInvalidValue;
   uint32_t* flags = nullptr; hipStream_t side; hipError_t e;
   if ((e = hipMallocAsync((void**)&flags, n * sizeof(uint32_t), s)) != hipSuccess) return e;
-  const bool ate = small_ate();
-  if ((e = guard_fork(s, &side)) != hipSuccess || (e = (ate ? launch_ate_guards(a, K, flags, n, side) : launch_short_loop_guards(a, K, flags, n, side))) != hipSuccess ||          // the unused slots repeat pair 0: same verdict
-      (e = (ate ? launch_dproduct_ate(a, K, nullptr, ok, n, err, s, kcount) : launch_dproduct(a, K, nullptr, ok, n, err, true, s, kcount))) != hipSuccess ||
+  if ((e = guard_fork(s, &side)) != hipSuccess || (e = launch_ate_guards(a, K, flags, n, side)) != hipSuccess ||          // the unused slots repeat pair 0: same verdict
+      (e = launch_dproduct_ate(a, K, nullptr, ok, n, err, s, kcount)) != hipSuccess ||
       (e = guard_join(s, side)) != hipSuccess) { (void)hipFreeAsync(flags, s); return e; }
   hipLaunchKernelGGL(k_product_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint32_t*)flags, ok, n);
   if ((e = hipFreeAsync(flags, s)) != hipSuccess) return e;
@@ -491,38 +484,32 @@ hipError_t launch_pairing_product_check(const PairArgs& a, int K, uint32_t* ok, 
   dim3 g((unsigned)((n + 63) / 64)), t(64);
   const bool small = n * (size_t)K <= dproduct_limit();
   if (K < 1 || K > 4) return hipErrorInvalidValue;
-  if (small) {                             // 127-step loops on the lane-distributed kernels, their preconditions checked beside them
+  if (small) {                             // the 63-step loop on the lane-distributed kernels, its preconditions checked beside it
     uint32_t* flags = nullptr; hipStream_t side; hipError_t e;
     if ((e = hipMallocAsync((void**)&flags, n * sizeof(uint32_t), s)) != hipSuccess) return e;
-    const bool sate = small_ate();
-    if ((e = guard_fork(s, &side)) != hipSuccess || (e = (sate ? launch_ate_guards(a, K, flags, n, side, p_trusted) : launch_short_loop_guards(a, K, flags, n, side))) != hipSuccess ||
-        (e = (sate ? launch_dproduct_ate(a, K, nullptr, ok, n, err, s) : launch_dproduct(a, K, nullptr, ok, n, err, true, s))) != hipSuccess ||
-        (e = guard_join(s, side)) != hipSuccess) { (void)hipFreeAsync(flags, s); return e; }
+    if ((e = guard_fork(s, &side)) != hipSuccess || (e = launch_ate_guards(a, K, flags, n, side, p_trusted)) != hipSuccess ||
+        (e = launch_dproduct_ate(a, K, nullptr, ok, n, err, s)) != hipSuccess || (e = guard_join(s, side)) != hipSuccess) { (void)hipFreeAsync(flags, s); return e; }
     hipLaunchKernelGGL(k_product_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint32_t*)flags, ok, n);
     if ((e = hipFreeAsync(flags, s)) != hipSuccess) return e;
   }
-  // large batches: the 63-step loop decides; what it marks (an argument outside its group) goes to the 255-step kernel as before.  ZKT_PRODUCT_LOOP=127 keeps
-  // the round-2 kernel (the twisted-ate loop over x^2) for A/B measurements.
-  static const bool ate = [] { const char* e = getenv("ZKT_PRODUCT_LOOP"); return !(e && atoi(e) == 127); }();
-  uint32_t* p_good = nullptr;
-  bool shared_untrusted = false;            // a G1 point shared by the batch that is not one of the library's own constants: tested once per launch (1.7 ms on one lane)
-  for (int k = 0; k < K; ++k) shared_untrusted = shared_untrusted || (a.s1[k] == 0 && !((p_trusted >> k) & 1));
-  if (!small && ate && shared_untrusted) {
+  // large batches: the 63-step loop decides; what it marks (an argument outside its group) goes to the 255-step kernel as before
+  uint32_t *p_good = nullptr, *fits = nullptr;
+  if (!small) {
+    bool shared_untrusted = false;          // a G1 point shared by the batch that is not one of the library's own constants: tested once per launch (1.7 ms on one lane)
+    for (int k = 0; k < K; ++k) shared_untrusted = shared_untrusted || (a.s1[k] == 0 && !((p_trusted >> k) & 1));
     hipError_t e;
-    if ((e = hipMallocAsync((void**)&p_good, sizeof(uint32_t), s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_shared_g1_guards, dim3(1), dim3(64), 0, s, a, K, p_good);
-  }
-  uint32_t* fits = nullptr;
-  if (!small && ate) {            // membership of the per-element G1 arguments at high occupancy (shared slots: p_good / p_trusted; their rows of `fits` are not read)
-    hipError_t e;
+    if (shared_untrusted) {
+      if ((e = hipMallocAsync((void**)&p_good, sizeof(uint32_t), s)) != hipSuccess) return e;
+      hipLaunchKernelGGL(k_shared_g1_guards, dim3(1), dim3(64), 0, s, a, K, p_good);
+    }
+    // membership of the per-element G1 arguments at high occupancy (shared slots: p_good / p_trusted; their rows of `fits` are not read)
     if ((e = hipMallocAsync((void**)&fits, (size_t)K * n * sizeof(uint32_t), s)) != hipSuccess) return e;
     G1Fits gf{};
     for (int k = 0; k < K; ++k) { gf.pts[k] = a.g1[k]; gf.stride[k] = a.s1[k]; }
     if ((e = launch_g1_fits(gf, K, fits, n, s)) != hipSuccess) { (void)hipFreeAsync(fits, s); return e; }
   }
-#define ZKT_PRODUCT_CHECK(KK) if (!small) { if (ate) hipLaunchKernelGGL((k_pairing_product_check_ate<KK>), g, t, 0, s, a, ok, n, err, (const uint32_t*)p_good, p_trusted, (const uint32_t*)fits); \
-                                            else hipLaunchKernelGGL((k_pairing_product_check<KK, true>), g, t, 0, s, a, ok, n, err, 0); } \
-                              hipLaunchKernelGGL((k_pairing_product_check<KK, false>), g, t, 0, s, a, ok, n, err, 1)
+#define ZKT_PRODUCT_CHECK(KK) if (!small) hipLaunchKernelGGL((k_pairing_product_check_ate<KK>), g, t, 0, s, a, ok, n, err, (const uint32_t*)p_good, p_trusted, (const uint32_t*)fits); \
+                              hipLaunchKernelGGL((k_pairing_product_check<KK>), g, t, 0, s, a, ok, n, err)
   switch (K) {
     case 1: ZKT_PRODUCT_CHECK(1); break;
     case 2: ZKT_PRODUCT_CHECK(2); break;

@@ -418,8 +418,7 @@ int zkt_pinocchio_prove_resident(zkt_pinocchio_pk* pk, const uint64_t* wires, co
 int zkt_pinocchio_verify(const zkt_pinocchio_crs* c, const zkt_pinocchio_proof* pf, const uint64_t* io_wires) {
   if (zkt_internal_ready() != ZKT_OK) return -ZKT_ERR_DEVICE;
   if (!c || !pf || (c->n_io && !io_wires)) return -ZKT_ERR_SHAPE;
-  static const bool fast = [] { const char* e = getenv("ZKT_PINOCCHIO_FAST_VERIFY"); return !e || atoi(e) != 0; }();
-  if (fast && c->n_io <= PIN_FAST_IO) { const int v = pin_verify_fast(c, pf, io_wires); if (v != PIN_FALL_BACK) return v; }
+  if (c->n_io <= PIN_FAST_IO) { const int v = pin_verify_fast(c, pf, io_wires); if (v != PIN_FALL_BACK) return v; }
   int rc;
   zkt_g1_affine t1, vwy;
   if ((rc = zkt_g1_add_batch(pf->v_mid_s, pf->g1_w_mid_s, &t1, 1)) || (rc = zkt_g1_add_batch(&t1, pf->y_mid_s, &vwy, 1))) return -rc;      // :44

@@ -8,7 +8,6 @@
 #include <mutex>
 #include <cstring>
 #include <cstdio>
-#include <functional>
 #include <memory>
 #include "abi.h"
 #include "zkt_internal.h"
@@ -231,21 +230,6 @@ __global__ void __launch_bounds__(256) k_dot(const uint32_t* __restrict__ a, con
   }
   if (t == 0) st_raw<C>(out, acc);
 }
-// the same dot product over many blocks: part[blockIdx] (Montgomery-free: canonical like k_dot's output), then k_sum over the parts.
-// One 256-thread block needs 0.6 ms for 65,536 elements; the range proof computes six of them on its critical path.
-template <class C>
-__global__ void __launch_bounds__(256) k_dot_parts(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, size_t n, uint32_t* __restrict__ part) {
-  __shared__ uint32_t lds[256 * C::N];
-  const int t = threadIdx.x;
-  Fp<C> acc = fp_zero<C>();
-  for (size_t i = (size_t)blockIdx.x * 256 + t; i < n; i += (size_t)gridDim.x * 256) acc = fp_add(acc, fp_mul(ld_fp<C>(a + i * C::N), ld_raw<C>(b + i * C::N)));
-  st_raw<C>(lds + t * C::N, acc); __syncthreads();
-  for (int d = 128; d >= 1; d >>= 1) {
-    if (t < d) { acc = fp_add(acc, ld_raw<C>(lds + (t + d) * C::N)); st_raw<C>(lds + t * C::N, acc); }
-    __syncthreads();
-  }
-  if (t == 0) st_raw<C>(part + blockIdx.x * C::N, acc);
-}
 // out[i] = a[i]*s0 + b[i]*s1 (a' = a_lo x + a_hi x^-1, bulletproofs.rs:49-50)
 template <class C>
 __global__ void __launch_bounds__(256) k_fold(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, const uint32_t* __restrict__ s0,
@@ -256,43 +240,13 @@ __global__ void __launch_bounds__(256) k_fold(const uint32_t* __restrict__ a, co
   st_raw<C>(out + i * C::N, r);
 }
 
-// out[i] = s  (PrimeFieldElem::repeat, prime_field_elem.rs:363-376) / out[i] = base^i (pow_seq, :346-361)
-template <class C>
-__global__ void __launch_bounds__(256) k_powseq(const uint32_t* __restrict__ base, size_t n, uint32_t* __restrict__ out) {
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  Fp<C> b = ld_fp<C>(base), r = fp_one<C>();
-  for (size_t e = i; e; e >>= 1) { if (e & 1) r = fp_mul(r, b); b = fp_sqr(b); }
-  st_fp<C>(out + i * C::N, r);
-}
-template <class C>
-__global__ void __launch_bounds__(256) k_scale(const uint32_t* __restrict__ a, const uint32_t* __restrict__ s, size_t n, uint32_t* __restrict__ out) {
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  st_raw<C>(out + i * C::N, fp_mul(ld_fp<C>(s), ld_raw<C>(a + i * C::N)));
-}
-template <class C>
-__global__ void __launch_bounds__(256) k_sum(const uint32_t* __restrict__ a, size_t n, uint32_t* __restrict__ out) {
-  __shared__ uint32_t lds[256 * C::N];
-  const int t = threadIdx.x;
-  Fp<C> acc = fp_zero<C>();
-  for (size_t i = t; i < n; i += 256) acc = fp_add(acc, ld_raw<C>(a + i * C::N));
-  st_raw<C>(lds + t * C::N, acc); __syncthreads();
-  for (int d = 128; d >= 1; d >>= 1) {
-    if (t < d) { acc = fp_add(acc, ld_raw<C>(lds + (t + d) * C::N)); st_raw<C>(lds + t * C::N, acc); }
-    __syncthreads();
-  }
-  if (t == 0) st_raw<C>(out, acc);
-}
-
 // ---- the range proof's vector algebra in ONE launch (bulletproofs.rs:72-127) -------------------------------------------------------
 // Every challenge is the caller's (injected), so nothing a lane computes for index i waits for anything but the proof's scalars:
 //   aR = aL - 1, l0 = aL - z, aRz = aR + z, r0 = y^i aRz + z^2 2^i, r1 = y^i sR, l = l0 + sL x, r = y^i (aRz + sR x) + z^2 2^i
 // and the scalar vectors of the five generator sums go straight into the MSM slots' buffers ([gg part | hh part], zkt_bp_ipa_ctx::dsc):
 //   slot 0: aL | aR      slot 1: sL | sR      slot 2: -z | (z y^i + z^2 2^i) y^-i      slot 3: sL x | sR x      slot 4 (no argument): l | r y^-i
 // The seven sums the scalar stage needs — t0 = <l0,r0>, t1 = <sL,r0> + <l0,r1>, t2 = <sL,r1>, <l,r>, v = <aL,2^n>, sum y^i, sum 2^i — leave as
-// per-block parts (k_rp_sums folds them).  The step-by-step form (one launch per vector operation, ~50 us each, ~40 of them) is kept behind
-// ZKT_RP_FUSED=0; both produce the same residues.
+// per-block parts (k_rp_sums folds them), instead of one launch per vector operation (~50 us each, ~40 of them).
 struct RpScalars { const uint32_t *y, *yinv, *z, *z2, *x; };
 struct RpOut { uint32_t *s0, *s1, *s2, *s3, *s4, *l, *r, *yinv_n, *parts; };
 template <class C>
@@ -452,8 +406,7 @@ std::vector<uint8_t> ate_key_bytes(const zkt_groth16_crs* c, size_t n_stmt) {
   return kb;
 }
 bool ate_key_applies(const zkt_groth16_crs* c, size_t n_stmt) {
-  static const bool off = [] { const char* e = getenv("ZKT_PRODUCT_LOOP"); return e && atoi(e) == 127; }();
-  return !off && n_stmt >= 1 && n_stmt <= 12 && c->g1_alpha && c->g2_beta;
+  return n_stmt >= 1 && n_stmt <= 12 && c->g1_alpha && c->g2_beta;
 }
 void ate_settle_locked(AteKey& e) {                                   // state 2 -> 0: the verdict
   if (e.state != 2) return;
@@ -745,7 +698,7 @@ struct zkt_bp_ipa_ctx {
 // The reference's one-shot calls (inner_product_argument, range_proof: bulletproofs.rs:19-55, 58-147) take the generators every time; a caller proves
 // many statements over ONE generator set.  The last context built by a one-shot call (window-multiple table of 2n+1 points, work buffers, fixed-base
 // tables: ~20 ms to set up at 65,536 generators) is kept and reused when the next call brings the same generators, byte for byte (host pointers only;
-// ZKT_BP_CTX_CACHE=0 turns this off; zkt_shutdown releases it).
+// zkt_shutdown releases it).
 namespace {
 struct BpCtxCache { std::mutex mu; std::vector<uint8_t> key; std::shared_ptr<zkt_bp_ipa_ctx> ctx; } g_bpc;
 bool bp_host_ptr(const void* p) {
@@ -754,8 +707,7 @@ bool bp_host_ptr(const void* p) {
   return a.type != hipMemoryTypeDevice;
 }
 std::shared_ptr<zkt_bp_ipa_ctx> bp_ctx_for(size_t n, const zkt_secp_affine* gg, const zkt_secp_affine* hh, const zkt_secp_affine* u, int* rc) {
-  static const bool enabled = [] { const char* e = getenv("ZKT_BP_CTX_CACHE"); return !e || atoi(e) != 0; }();
-  const bool cacheable = enabled && bp_host_ptr(gg) && bp_host_ptr(hh) && bp_host_ptr(u);
+  const bool cacheable = bp_host_ptr(gg) && bp_host_ptr(hh) && bp_host_ptr(u);
   const size_t nb = n * SPB;
   std::unique_lock<std::mutex> lk(g_bpc.mu, std::defer_lock);
   if (cacheable) {
@@ -998,21 +950,6 @@ static int range_proof_core(zkt_bp_ipa_ctx* c, const zkt_secp_affine* V, const u
   int vi = 0, si = 0;
   auto newv = [&]() { return vec.w() + (size_t)(vi++) * n * 8; };
   auto news = [&]() { return sc.w() + (size_t)(si++) * 8; };
-  auto op = [&](int o, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t cnt) { return launch_fp_op(F_SN, o, a, b, out, cnt, noerr, s) == hipSuccess; };
-  auto vadd = [&](const uint32_t* a, const uint32_t* b) { uint32_t* o = newv(); op(OP_ADD, a, b, o, n); return o; };
-  auto vsub = [&](const uint32_t* a, const uint32_t* b) { uint32_t* o = newv(); op(OP_SUB, a, b, o, n); return o; };
-  auto vhad = [&](const uint32_t* a, const uint32_t* b) { uint32_t* o = newv(); op(OP_MUL, a, b, o, n); return o; };
-  std::function<void()> flush_scalars = [] {};          // set below, once the queue of one-element operations exists: whoever reads a scalar runs it first
-  auto vscl = [&](const uint32_t* a, const uint32_t* k) { flush_scalars(); uint32_t* o = newv(); hipLaunchKernelGGL(k_scale<SnC>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, k, n, o); return o; };
-  auto vpow = [&](const uint32_t* b) { flush_scalars(); uint32_t* o = newv(); hipLaunchKernelGGL(k_powseq<SnC>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b, n, o); return o; };
-  auto vsum = [&](const uint32_t* a) { uint32_t* o = news(); hipLaunchKernelGGL(k_sum<SnC>, dim3(1), dim3(256), 0, s, a, n, o); return o; };
-  const View dparts = carve(64 * FRB);
-  auto vdot = [&](const uint32_t* a, const uint32_t* b) {
-    uint32_t* o = news();
-    if (n < 4096) { hipLaunchKernelGGL(k_dot<SnC>, dim3(1), dim3(256), 0, s, a, b, n, o); return o; }
-    hipLaunchKernelGGL(k_dot_parts<SnC>, dim3(64), dim3(256), 0, s, a, b, n, dparts.w());          // stream order keeps the shared parts buffer safe
-    hipLaunchKernelGGL(k_sum<SnC>, dim3(1), dim3(256), 0, s, (const uint32_t*)dparts.w(), (size_t)64, o);
-    return o; };
   // one-element operations are queued and run as ONE launch (launch_scalar_ops) when something is about to read their results: a launch per
   // operation is ~50 us of a chain of ~35
   ScalarOps pend{}; bool sok = true;
@@ -1021,13 +958,10 @@ static int range_proof_core(zkt_bp_ipa_ctx* c, const zkt_secp_affine* V, const u
   auto sadd = [&](const uint32_t* a, const uint32_t* b) { return sop(OP_ADD, a, b); };
   auto ssub = [&](const uint32_t* a, const uint32_t* b) { return sop(OP_SUB, a, b); };
   auto smul = [&](const uint32_t* a, const uint32_t* b) { return sop(OP_MUL, a, b); };
-  auto sneg = [&](const uint32_t* a) { return sop(OP_NEG, a, nullptr); };
   auto sinv = [&](const uint32_t* a) { return sop(OP_INV, a, nullptr); };
-  flush_scalars = sflush;
   auto sput = [&](const uint64_t* hsrc) { uint32_t* o = news(); hipMemcpyAsync(o, hsrc, FRB, hipMemcpyHostToDevice, s); return o; };
   auto vput = [&](const uint64_t* hsrc) { uint32_t* o = newv(); hipMemcpyAsync(o, hsrc, n * FRB, hipMemcpyHostToDevice, s); return o; };
   unsigned long long ne = NO_ERR; hipMemcpyAsync(derr.p, &ne, 8, hipMemcpyHostToDevice, s);
-  const uint64_t one64[4] = {1, 0, 0, 0}, two64[4] = {2, 0, 0, 0};
   if ((rnd[8] | rnd[9] | rnd[10] | rnd[11]) == 0) return -ZKT_ERR_INV_ZERO;   // y must be invertible (:109); the reference draws non-zero values
   // The generators stay resident for the whole proof: one base set [gg | hh | u] (zkt_bp_ipa_ctx) serves every (AffinePoints * PrimeFieldElems).sum()
   // as an MSM and the inner-product argument itself.  hh' = hh * y^-i (:109) is never materialised: a sum over hh' with scalars v is the sum over hh
@@ -1046,14 +980,7 @@ static int range_proof_core(zkt_bp_ipa_ctx* c, const zkt_secp_affine* V, const u
   auto seg = [&](const uint32_t* P, const uint32_t* k, uint32_t* out) { return MulSeg{P, k, out, 1u, 0u, 0u}; };
   auto run = [&](const MulSegs& m) { okl = okl && launch_group_mul_segs(G_SECP, m, 8, s) == hipSuccess; };
   auto padd = [&](const uint32_t* a, const uint32_t* b, uint32_t* o) { okl = okl && launch_group_add(G_SECP, a, b, o, 1, s) == hipSuccess; return o; };
-  // sum_k gg[k] vg[k] + hh[k] vh[k] in MSM slot `slot` (scalars [vg | vh | 0] in the slot's buffer)
   int n_sub = 0;
-  auto msm_sub = [&](int slot, const uint32_t* vg, const uint32_t* vh) {
-    uint32_t* buf = c->dsc.w() + (size_t)slot * NB * 8;
-    okl = okl && hipMemcpyAsync(buf, vg, n * FRB, hipMemcpyDeviceToDevice, s) == hipSuccess && hipMemcpyAsync(buf + n * 8, vh, n * FRB, hipMemcpyDeviceToDevice, s) == hipSuccess &&
-          hipMemsetAsync(buf + 2 * n * 8, 0, FRB, s) == hipSuccess && zkt_secp_msm_submit(c->set, (const uint64_t*)buf, NB, s, slot) == ZKT_OK;
-    if (okl) n_sub = slot + 1;
-  };
   zkt_secp_affine hres[5];
   int n_col = 0;
   bool ipa_started = false;                                                           // the inner-product argument's own MSM, in flight on IPA_SLOT beside the proof's
@@ -1067,75 +994,38 @@ static int range_proof_core(zkt_bp_ipa_ctx* c, const zkt_secp_affine* V, const u
 
   uint32_t *d_aL = vput(aL), *d_sL = vput(rnd + 28), *d_sR = vput(rnd + 28 + 4 * n);
   uint32_t *alpha = sput(rnd), *rho = sput(rnd + 4), *y = sput(rnd + 8), *z = sput(rnd + 12), *tau1 = sput(rnd + 16), *tau2 = sput(rnd + 20), *x = sput(rnd + 24);
-  uint32_t *d_gamma = sput(gamma), *one = sput(one64), *two = sput(two64);
-  uint32_t *z2, *yinv_n, *t1, *t2, *t_hat, *tau_x, *mu, *l, *r, *lr, *k_g, *k_h, *two_n = nullptr, *v_val = nullptr;
-  static const bool fused = [] { const char* e = getenv("ZKT_RP_FUSED"); return !e || atoi(e) != 0; }();
+  uint32_t* d_gamma = sput(gamma);
   const View dparts7 = carve(7 * ((n + 255) / 256) * FRB);
-  if (fused) {                                                                        // the whole vector stage in one launch (k_rp_fused)
-    z2 = smul(z, z);
-    uint32_t *yinv = sinv(y), *x2 = smul(x, x), *z3 = smul(z2, z);
-    sflush();
-    auto slot = [&](int k) { return c->dsc.w() + (size_t)k * NB * 8; };
-    l = newv(); r = newv(); yinv_n = newv();
-    uint32_t* sums = news(); for (int q = 1; q < 7; ++q) (void)news();                 // seven consecutive scalars
-    const size_t nblk = (n + 255) / 256;
-    hipLaunchKernelGGL(k_rp_fused<SnC>, dim3((unsigned)nblk), dim3(256), 0, s, (const uint32_t*)d_aL, (const uint32_t*)d_sL, (const uint32_t*)d_sR,
-                       RpScalars{y, yinv, z, z2, x}, n, RpOut{slot(0), slot(1), slot(2), slot(3), use_ipa ? nullptr : slot(4), l, r, yinv_n, dparts7.w()});
-    hipLaunchKernelGGL(k_rp_sums<SnC>, dim3(7), dim3(256), 0, s, (const uint32_t*)dparts7.w(), nblk, sums);
-    for (int k = 0; k < (use_ipa ? 4 : 5); ++k) { okl = okl && zkt_secp_msm_submit(c->set, (const uint64_t*)slot(k), NB, s, k) == ZKT_OK; if (okl) n_sub = k + 1; }
-    // The argument's scalar stage and its one MSM need l, r and the challenges only — its P enters at the very end — so it starts NOW and runs beside the
-    // proof's own generator sums.  The reference reaches it only after :116-118 hold; a proof that fails there is rejected below whatever the argument says,
-    // and a zero challenge (its error) keeps the sequential order.
-    if (use_ipa && c->levels >= 1 && xs) {
-      bool nz = true;
-      for (size_t lv = 0; lv < c->levels && nz; ++lv) nz = (xs[lv * 4] | xs[lv * 4 + 1] | xs[lv * 4 + 2] | xs[lv * 4 + 3]) != 0;
-      if (nz && okl) { okl = ipa_verdict_submit(c, (const uint64_t*)l, (const uint64_t*)r, xs, yinv_n, s, IPA_SLOT) == ZKT_OK; ipa_started = okl; }      // (a side stream for its ~1 ms of small kernels measured no better: 6.5 against 6.2 ms)
-    }
-    uint32_t *t0 = sums, *sum_y = sums + 5 * 8, *sum_2 = sums + 6 * 8;
-    t1 = sums + 8; t2 = sums + 16; lr = sums + 24; v_val = sums + 32;
-    t_hat = sadd(sadd(t0, smul(t1, x)), smul(t2, x2));                                // :104
-    tau_x = sadd(sadd(smul(tau2, x2), smul(tau1, x)), smul(z2, d_gamma));             // :105
-    mu = sadd(alpha, smul(rho, x));                                                   // :106
-    uint32_t* delta_yz = ssub(smul(ssub(z, z2), sum_y), smul(z3, sum_2));             // :112
-    k_g = sadd(sadd(delta_yz, smul(t1, x)), smul(t2, x2));
-    k_h = sadd(smul(tau1, x), smul(tau2, x2));
-  } else {
-    uint32_t* one_n = vpow(one); two_n = vpow(two);                                   // :72-73
-    uint32_t* aR = vsub(d_aL, one_n);                                                   // :75
-    msm_sub(0, d_aL, aR);                                                               // (gg*aL).sum() + (hh*aR).sum()   of A (:77)
-    msm_sub(1, d_sL, d_sR);                                                             // (gg*sL).sum() + (hh*sR).sum()   of S (:82)
-    uint32_t* y_n = vpow(y);                                                            // :87
-    z2 = smul(z, z);
-    yinv_n = vpow(sinv(y));                                                   // hh' = hh * y^-i (:109), as coefficients
-    uint32_t* twoz2 = vscl(two_n, z2);
-    // the challenges are the caller's (injected), so the two generator sums that depend on them only through cheap vector kernels are submitted NOW
-    // and run beside A's and S's: four MSMs in flight while the dot-product chain below proceeds
-    uint32_t *sLx = vscl(d_sL, x), *sRx = vscl(d_sR, x);
-    msm_sub(2, vscl(one_n, sneg(z)), vhad(vadd(vscl(y_n, z), twoz2), yinv_n));          // gg * (-z 1^n) + hh' * (z y^n + z^2 2^n)  of P (:126-127)
-    msm_sub(3, sLx, sRx);                                                               // x * ((gg*sL).sum() + (hh*sR).sum()): the generator part of S x (:124)
-    uint32_t* onez = vscl(one_n, z);
-    uint32_t* l0 = vsub(d_aL, onez);                                                    // :88
-    uint32_t* aRz = vadd(aR, onez);
-    uint32_t* r0 = vadd(vhad(y_n, aRz), twoz2);                                         // :90
-    uint32_t* r1 = vhad(y_n, d_sR);                                                     // :91
-    uint32_t* t0 = vdot(l0, r0); t1 = sadd(vdot(d_sL, r0), vdot(l0, r1)); t2 = vdot(d_sL, r1);   // :93-95
-    uint32_t* x2 = smul(x, x);
-    t_hat = sadd(sadd(t0, smul(t1, x)), smul(t2, x2));                        // :104
-    tau_x = sadd(sadd(smul(tau2, x2), smul(tau1, x)), smul(z2, d_gamma));     // :105
-    mu = sadd(alpha, smul(rho, x));                                           // :106
-    uint32_t* z3 = smul(z2, z);
-    uint32_t* delta_yz = ssub(smul(ssub(z, z2), vsum(y_n)), smul(z3, vsum(two_n)));     // :112 (one_n o v = v)
-    l = vadd(l0, sLx);                                                        // :121
-    r = vadd(vhad(y_n, vadd(aRz, sRx)), twoz2);                               // :122
-    lr = vdot(l, r);
-    // Every single-point product is a ~4 ms dependent chain however few points a launch covers, so ALL of them go out in ONE launch: the products the
-    // reference takes of T1, T2 and S (:115, :124) are rewritten on the fixed points — T1 x = g (t1 x) + h (tau1 x), S x = h (rho x) + sum over the
-    // generators with scalars sL x, sR x (one more MSM) — the same group elements, so A, S, T1, T2, P keep their bits.
-    uint32_t *t1x = smul(t1, x), *t2x2 = smul(t2, x2);
-    k_g = sadd(sadd(delta_yz, t1x), t2x2);                                    // rhs of :115 = V z^2 + g (delta + t1 x + t2 x^2) + h (tau1 x + tau2 x^2)
-    k_h = sadd(smul(tau1, x), smul(tau2, x2));
-    if (!use_ipa) msm_sub(4, l, vhad(r, yinv_n));                                       // (gg*l).sum() + (hh'*r).sum()  (:142)
+  // the whole vector stage in one launch (k_rp_fused)
+  uint32_t* z2 = smul(z, z);
+  uint32_t *yinv = sinv(y), *x2 = smul(x, x), *z3 = smul(z2, z);
+  sflush();
+  auto slot = [&](int k) { return c->dsc.w() + (size_t)k * NB * 8; };
+  uint32_t *l = newv(), *r = newv(), *yinv_n = newv();
+  uint32_t* sums = news(); for (int q = 1; q < 7; ++q) (void)news();                 // seven consecutive scalars
+  const size_t nblk = (n + 255) / 256;
+  hipLaunchKernelGGL(k_rp_fused<SnC>, dim3((unsigned)nblk), dim3(256), 0, s, (const uint32_t*)d_aL, (const uint32_t*)d_sL, (const uint32_t*)d_sR,
+                     RpScalars{y, yinv, z, z2, x}, n, RpOut{slot(0), slot(1), slot(2), slot(3), use_ipa ? nullptr : slot(4), l, r, yinv_n, dparts7.w()});
+  hipLaunchKernelGGL(k_rp_sums<SnC>, dim3(7), dim3(256), 0, s, (const uint32_t*)dparts7.w(), nblk, sums);
+  for (int k = 0; k < (use_ipa ? 4 : 5); ++k) { okl = okl && zkt_secp_msm_submit(c->set, (const uint64_t*)slot(k), NB, s, k) == ZKT_OK; if (okl) n_sub = k + 1; }
+  // The argument's scalar stage and its one MSM need l, r and the challenges only — its P enters at the very end — so it starts NOW and runs beside the
+  // proof's own generator sums.  The reference reaches it only after :116-118 hold; a proof that fails there is rejected below whatever the argument says,
+  // and a zero challenge (its error) keeps the sequential order.
+  if (use_ipa && c->levels >= 1 && xs) {
+    bool nz = true;
+    for (size_t lv = 0; lv < c->levels && nz; ++lv) nz = (xs[lv * 4] | xs[lv * 4 + 1] | xs[lv * 4 + 2] | xs[lv * 4 + 3]) != 0;
+    if (nz && okl) { okl = ipa_verdict_submit(c, (const uint64_t*)l, (const uint64_t*)r, xs, yinv_n, s, IPA_SLOT) == ZKT_OK; ipa_started = okl; }      // (a side stream for its ~1 ms of small kernels measured no better: 6.5 against 6.2 ms)
   }
+  uint32_t *t0 = sums, *t1 = sums + 8, *t2 = sums + 16, *lr = sums + 24, *v_val = sums + 32, *sum_y = sums + 5 * 8, *sum_2 = sums + 6 * 8;
+  uint32_t* t_hat = sadd(sadd(t0, smul(t1, x)), smul(t2, x2));                      // :104
+  uint32_t* tau_x = sadd(sadd(smul(tau2, x2), smul(tau1, x)), smul(z2, d_gamma));   // :105
+  uint32_t* mu = sadd(alpha, smul(rho, x));                                         // :106
+  uint32_t* delta_yz = ssub(smul(ssub(z, z2), sum_y), smul(z3, sum_2));             // :112
+  // Every single-point product is a ~4 ms dependent chain however few points a launch covers, so ALL of them go out in ONE launch: the products the
+  // reference takes of T1, T2 and S (:115, :124) are rewritten on the fixed points — T1 x = g (t1 x) + h (tau1 x), S x = h (rho x) + sum over the
+  // generators with scalars sL x, sR x (one more MSM) — the same group elements, so A, S, T1, T2, P keep their bits.
+  uint32_t* k_g = sadd(sadd(delta_yz, smul(t1, x)), smul(t2, x2));                  // rhs of :115 = V z^2 + g (delta + t1 x + t2 x^2) + h (tau1 x + tau2 x^2)
+  uint32_t* k_h = sadd(smul(tau1, x), smul(tau2, x2));
   // ... and every one of them is on a FIXED point but one: g, h, u get 64-entry tables of their 16^w multiples (built when the context first sees
   // the point, ~4 ms once) and a product is one wave adding 64 partial products (~0.2 ms).  The exception is V z^2 (:115): V is the caller's.  For
   // the V this proof is about — V = g v + h gamma, v = <aL, 2^n> — it equals g (v z^2) + h (gamma z^2), which folds into the other two terms of
@@ -1154,7 +1044,6 @@ static int range_proof_core(zkt_bp_ipa_ctx* c, const zkt_secp_affine* V, const u
     if (need_h) { c->fix_h = *h; c->fix_h_ok = okl; }
     if (need_u) c->fix_u_ok = okl;
   }
-  if (!v_val) v_val = vdot(d_aL, two_n);                                              // v = <aL, 2^n> (:75: the value the bits are of)
   uint32_t *kg_v = sadd(k_g, smul(v_val, z2)), *kh_v = sadd(k_h, smul(d_gamma, z2));
   {
     FixedMuls m{}; int k = 0;
