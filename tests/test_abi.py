@@ -42,6 +42,17 @@ def test_gt_eq_is_plain_memory_equality():
     assert L.zkt_gt_eq(ptr(a), ptr(b)) == 0
 
 
+def test_generators_match_the_oracle_word_for_word():
+    """zkt_{g1,g2,secp}_generator copy out the one definition of each generator (csrc/host_abi.h) that the protocols upload too; no device needed"""
+    L, O = zk.lib(), oracle()
+    for name, words in (("g1", G1W), ("g2", G2W), ("secp", 9)):
+        got = np.full(words, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+        want = np.zeros(words, dtype=np.uint64)
+        getattr(L, f"zkt_{name}_generator")(ptr(got))
+        getattr(O, f"zkto_{name}_generator")(ptr(want))
+        assert (got == want).all(), name
+
+
 def test_comm_shard_range_rejects_bad_ranks_and_library_needs_no_rccl_at_load_time():
     """zkt_comm_shard_range is pure host arithmetic: world < 1 or a rank outside [0, world) yields the empty range (it used to divide by zero);
     and RCCL is opened on first use, so a single-GPU consumer of libzkt_hip.so does not link it."""

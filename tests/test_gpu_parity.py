@@ -133,6 +133,15 @@ def test_fq_mul_large_kat(L):                   # prime_field_elem.rs:600-617 is
     assert arr_to_ints(o) == [15]
 
 
+def test_failed_allocation_leaves_no_stale_error(L):
+    """A staging size far beyond any device's memory (2^40 Fq elements) is refused by the arena's hipMalloc before any copy or kernel; that
+    failure must not linger in the runtime's last error, where the next call's launcher (which ends in hipGetLastError) would report it as its own."""
+    a = ints_to_arr([Q - 3, 2, 5, Q - 1], 6); b = ints_to_arr([Q - 5, 3, 7, 2], 6); o = np.zeros_like(a)
+    assert L.zkt_fq_mul_batch(ptr(a), ptr(b), ptr(o), ctypes.c_size_t(1 << 40)) == ZKT_ERR_DEVICE
+    assert L.zkt_fq_mul_batch(ptr(a), ptr(b), ptr(o), ctypes.c_size_t(4)) == ZKT_OK
+    assert arr_to_ints(o) == [15, 6, 35, Q - 2]
+
+
 a1, b1, c1, d1 = Q - 3, Q - 5, Q - 7, Q - 9        # fq_test_helper.rs:9-34
 a2, b2, c2, d2 = (a1, b1), (b1, c1), (c1, d1), (d1, a1)
 a6, b6, c6, d6 = a2 + b2 + c2, b2 + c2 + d2, c2 + d2 + a2, d2 + a2 + b2

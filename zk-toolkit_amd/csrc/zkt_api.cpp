@@ -10,6 +10,7 @@
 #include "../../include/zkt.h"
 #include "zkt_internal.h"
 #include "zkt_constants.h"
+#include "host_abi.h"
 static_assert(ZKT_G1_PARTIAL_WORDS == 3 * zkt::FqC::N && ZKT_G2_PARTIAL_WORDS == 6 * zkt::FqC::N && ZKT_SECP_PARTIAL_WORDS == 3 * zkt::SpC::N,
               "include/zkt.h partial sizes follow the internal limb layout");
 
@@ -30,8 +31,6 @@ Ctx g;
 thread_local size_t t_err_index = 0;
 thread_local float t_kernel_ms = 0.f;
 thread_local const char* t_kernel_name = "";
-
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[zkt] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return ZKT_ERR_DEVICE; } } while (0)
 
 // every entry point starts here: the library owns ONE device (zkt_init), and a thread's current HIP device is per-thread state,
 // so it is set on entry — handles, streams and workspaces are then always created and used on that device
@@ -147,7 +146,6 @@ int tower_batch(int deg, int op, const uint64_t* a, const uint64_t* b, uint64_t*
   return staged(a, w, binary ? b : nullptr, binary ? w : 0, out, w, n, ZKT_ERR_INV_ZERO,
                 [&](uint32_t* da, uint32_t* db, uint32_t* dout, hipStream_t s) { return launch_tower_op(deg, op, da, db, dout, n, g.d_err, s); });
 }
-size_t pt_bytes(int grp) { return grp == G_G1 ? sizeof(zkt_g1_affine) : grp == G_G2 ? sizeof(zkt_g2_affine) : sizeof(zkt_secp_affine); }
 
 }  // namespace
 
@@ -185,7 +183,6 @@ struct zkt_bases_impl {               // one resident base set of any group; zkt
 struct zkt_g1_bases : zkt_bases_impl {};
 struct zkt_g2_bases : zkt_bases_impl {};
 struct zkt_secp_bases : zkt_bases_impl {};
-static size_t grp_pt_bytes(int grp) { return grp == G_G1 ? sizeof(zkt_g1_affine) : grp == G_G2 ? sizeof(zkt_g2_affine) : sizeof(zkt_secp_affine); }
 static size_t grp_coord_bytes(int grp) { return 4 * (grp == G_G1 ? zkt::FqC::N : grp == G_G2 ? 2 * zkt::FqC::N : zkt::SpC::N); }   // internal (Montgomery) coordinate
 static int streams_ready(zkt_bases_impl* h) {
   if (h->grouped || !h->own_streams || (h->s_acc && h->s_sort && h->s_tail[zkt_bases_impl::NTAIL - 1])) return ZKT_OK;
@@ -214,8 +211,8 @@ static int slot_ready(zkt_bases_impl* h, int k) {   // lazily create the slot's 
   HIPCHK(hipMalloc(&S.workspace, h->plan.ws_bytes));
   if (debug_poison()) { HIPCHK(hipMemset(S.workspace, 0xA5, h->plan.ws_bytes)); HIPCHK(hipDeviceSynchronize()); }
   HIPCHK(hipMalloc((void**)&S.d_result_jac, 3 * grp_coord_bytes(h->grp)));
-  HIPCHK(hipMalloc((void**)&S.d_out_abi, grp_pt_bytes(h->grp)));
-  HIPCHK(hipHostMalloc((void**)&S.h_out, grp_pt_bytes(h->grp), hipHostMallocDefault));
+  HIPCHK(hipMalloc((void**)&S.d_out_abi, abi_pt_bytes(h->grp)));
+  HIPCHK(hipHostMalloc((void**)&S.h_out, abi_pt_bytes(h->grp), hipHostMallocDefault));
   return ZKT_OK;
 }
 
@@ -256,7 +253,6 @@ int zkt_init(int device) {
   g.ready = true;
   return ZKT_OK;
 }
-extern "C" void zkt_internal_clear_caches();       // zkt_protocols.hip
 static void tate_events_release();
 void zkt_shutdown(void) {
   if (g.ready) (void)hipSetDevice(g.device);
@@ -347,18 +343,18 @@ int zkt_debug_dfq12_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* o
 }
 
 static int group_add(int grp, const void* a, const void* b, void* out, size_t n) {
-  size_t w = pt_bytes(grp);
+  size_t w = abi_pt_bytes(grp);
   return staged(a, w, b, w, out, w, n, ZKT_ERR_SHAPE,
                 [&](uint32_t* da, uint32_t* db, uint32_t* dout, hipStream_t s) { return launch_group_add(grp, da, db, dout, n, s); });
 }
 static int group_neg(int grp, const void* a, void* out, size_t n) {
-  size_t w = pt_bytes(grp);
+  size_t w = abi_pt_bytes(grp);
   return staged(a, w, nullptr, 0, out, w, n, ZKT_ERR_SHAPE,
                 [&](uint32_t* da, uint32_t*, uint32_t* dout, hipStream_t s) { return launch_group_neg(grp, da, dout, n, s); });
 }
 static int group_mul(int grp, const void* pts, const uint64_t* scalars, int limbs, void* out, size_t n) {
   if (limbs < 1 || limbs > 6) return ZKT_ERR_SHAPE;
-  size_t w = pt_bytes(grp);
+  size_t w = abi_pt_bytes(grp);
   return staged(pts, w, scalars, (size_t)limbs * 8, out, w, n, ZKT_ERR_SHAPE,
                 [&](uint32_t* da, uint32_t* db, uint32_t* dout, hipStream_t s) { return launch_group_mul(grp, da, db, limbs * 2, dout, n, s); });
 }
@@ -366,7 +362,7 @@ static int group_mul(int grp, const void* pts, const uint64_t* scalars, int limb
 // AffinePoints * PrimeFieldElem (:105-122): every point times ONE scalar
 static int group_sum(int grp, const void* pts, size_t n, void* out) {
   if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  const size_t w = pt_bytes(grp);
+  const size_t w = abi_pt_bytes(grp);
   if (!out || (n && !pts)) return ZKT_ERR_SHAPE;
   if (n == 0) { memset(out, 0, w); ((uint32_t*)out)[w / 4 - 2] = 1; return ZKT_OK; }
   std::lock_guard<std::mutex> lk(g.mu);
@@ -389,7 +385,7 @@ static int group_sum(int grp, const void* pts, size_t n, void* out) {
 static int group_scale(int grp, const void* pts, const uint64_t* k, int limbs, void* out, size_t n) {
   if (limbs < 1 || limbs > 6) return ZKT_ERR_SHAPE;
   if (n == 0) return ensure_ready();
-  size_t w = pt_bytes(grp);
+  size_t w = abi_pt_bytes(grp);
   return staged_raw(pts, w * n, k, (size_t)limbs * 8, out, w * n, ZKT_ERR_SHAPE,
                     [&](uint32_t* da, uint32_t* db, uint32_t* dout, hipStream_t s) { return launch_group_mul(grp, da, db, limbs * 2, dout, n, s, false, true); });
 }
@@ -410,12 +406,12 @@ int zkt_secp_mul_batch(const zkt_secp_affine* p, const uint64_t* k, int l, zkt_s
 
 // a16: is_rational_point / order-r membership / generators
 static int group_pred(int grp, int pred, const void* pts, uint32_t* out, size_t n) {
-  static const uint32_t R_WORDS[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};      // params.rs:14
-  static const uint32_t SN_WORDS[8] = {0xd0364141u, 0xbfd25e8cu, 0xaf48a03bu, 0xbaaedce6u, 0xfffffffeu, 0xffffffffu, 0xffffffffu, 0xffffffffu};   // secp256k1 n
-  return staged(pts, pt_bytes(grp), grp == G_SECP ? SN_WORDS : R_WORDS, 0, out, 4, n, ZKT_ERR_SHAPE,
+  uint32_t order[8];                                                        // r (params.rs:14) or secp256k1's n
+  for (int i = 0; i < 8; ++i) order[i] = grp == G_SECP ? SnC::mod32(i) : FrC::mod32(i);
+  return staged(pts, abi_pt_bytes(grp), nullptr, 0, out, 4, n, ZKT_ERR_SHAPE,
                 [&](uint32_t* da, uint32_t*, uint32_t* dout, hipStream_t s) -> hipError_t {
                   uint32_t* d_order = g.d_small;                           // g.mu is held by staged_raw
-                  hipError_t e = hipMemcpyAsync(d_order, grp == G_SECP ? SN_WORDS : R_WORDS, 32, hipMemcpyHostToDevice, s);
+                  hipError_t e = hipMemcpyAsync(d_order, order, 32, hipMemcpyHostToDevice, s);
                   if (e != hipSuccess) return e;
                   return launch_group_pred(grp, pred, da, d_order, 8, dout, n, s);
                 });
@@ -426,36 +422,9 @@ int zkt_secp_is_on_curve_batch(const zkt_secp_affine* p, uint32_t* out, size_t n
 int zkt_g1_in_subgroup_batch(const zkt_g1_affine* p, uint32_t* out, size_t n) { return group_pred(G_G1, 1, p, out, n); }
 int zkt_g2_in_subgroup_batch(const zkt_g2_affine* p, uint32_t* out, size_t n) { return group_pred(G_G2, 1, p, out, n); }
 int zkt_secp_in_subgroup_batch(const zkt_secp_affine* p, uint32_t* out, size_t n) { return group_pred(G_SECP, 1, p, out, n); }
-static void put_limbs(uint64_t* dst, const char* hex, int limbs) {           // big-endian hex literal -> little-endian u64 limbs
-  const size_t len = strlen(hex);
-  for (int i = 0; i < limbs; ++i) {
-    uint64_t v = 0;
-    for (int d = 0; d < 16; ++d) {
-      const long pos = (long)len - 16 * (i + 1) + d;
-      if (pos < 0) continue;
-      const char c = hex[pos];
-      v = (v << 4) | (uint64_t)(c <= '9' ? c - '0' : (c | 32) - 'a' + 10);
-    }
-    dst[i] = v;
-  }
-}
-void zkt_g1_generator(zkt_g1_affine* out) {                                   // g1_point.rs:38-47
-  memset(out, 0, sizeof(*out));
-  put_limbs(out->x, "17f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83ff97a1aeffb3af00adb22c6bb", 6);
-  put_limbs(out->y, "08b3f481e3aaa0f1a09e30ed741d8ae4fcf5e095d5d00af600db18cb2c04b3edd03cc744a2888ae40caa232946c5e7e1", 6);
-}
-void zkt_g2_generator(zkt_g2_affine* out) {                                   // g2_point.rs:36-46; Fq2 = {u1, u0}
-  memset(out, 0, sizeof(*out));
-  put_limbs(out->x, "13e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bbdc7f5049334cf11213945d57e5ac7d055d042b7e", 6);
-  put_limbs(out->x + 6, "024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8", 6);
-  put_limbs(out->y, "0606c4a02ea734cc32acd2b02bc28b99cb3e287e85a763af267492ab572e99ab3f370d275cec1da1aaa9075ff05f79be", 6);
-  put_limbs(out->y + 6, "0ce5d527727d6e118cc9cdc6da2e351aadfd9baa8cbdd3a76d429a695160d12c923ac9cc3baca289e193548608b82801", 6);
-}
-void zkt_secp_generator(zkt_secp_affine* out) {                               // secp256k1/affine_point.rs:40-47
-  memset(out, 0, sizeof(*out));
-  put_limbs(out->x, "79be667ef9dcbbac55a06295ce870b07029bfcdb2dce28d959f2815b16f81798", 4);
-  put_limbs(out->y, "483ada7726a3c4655da4fbfc0e1108a8fd17b448a68554199c47d08ffb10d4b8", 4);
-}
+void zkt_g1_generator(zkt_g1_affine* out) { *out = G1_GEN; }
+void zkt_g2_generator(zkt_g2_affine* out) { *out = G2_GEN; }
+void zkt_secp_generator(zkt_secp_affine* out) { *out = SECP_GEN; }
 
 int zkt_tate_batch(const zkt_g1_affine* g1, const zkt_g2_affine* g2, uint64_t* out, size_t n) {
   return staged(g1, sizeof(zkt_g1_affine), g2, sizeof(zkt_g2_affine), out, 576, n, ZKT_ERR_INFINITY,
@@ -575,8 +544,8 @@ static int bases_upload(int grp, const void* host, size_t n, zkt_bases_impl** ou
   if (!out || (n && !host)) return ZKT_ERR_SHAPE;
   HIPCHK(hipSetDevice(g.device));
   uint32_t* tmp = nullptr;
-  HIPCHK(hipMalloc((void**)&tmp, (n ? n : 1) * grp_pt_bytes(grp)));
-  if (n) HIPCHK(hipMemcpy(tmp, host, n * grp_pt_bytes(grp), hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc((void**)&tmp, (n ? n : 1) * abi_pt_bytes(grp)));
+  if (n) HIPCHK(hipMemcpy(tmp, host, n * abi_pt_bytes(grp), hipMemcpyHostToDevice));
   int rc = bases_from_device(grp, tmp, n, g.stream, out);
   hipFree(tmp);
   return rc;
@@ -622,7 +591,7 @@ static int msm_submit_locked(zkt_bases_impl* h, const uint64_t* dev_scalars, siz
       S.gkey[hit] = (const void*)dev_scalars;
     }
     HIPCHK(hipGraphLaunch(S.gexec[hit], st));
-    HIPCHK(hipMemcpyAsync(S.h_out, S.d_out_abi, grp_pt_bytes(h->grp), hipMemcpyDeviceToHost, st));      // kernels only inside the graph: the copy of the result follows it on the stream
+    HIPCHK(hipMemcpyAsync(S.h_out, S.d_out_abi, abi_pt_bytes(h->grp), hipMemcpyDeviceToHost, st));      // kernels only inside the graph: the copy of the result follows it on the stream
     HIPCHK(hipEventRecord(S.e_done, st));
     S.timed = false; S.busy = true;
     return ZKT_OK;
@@ -639,7 +608,7 @@ static int msm_submit_locked(zkt_bases_impl* h, const uint64_t* dev_scalars, siz
   HIPCHK(hipEventRecord(S.e_acc1, sa));
   HIPCHK(hipStreamWaitEvent(st, S.e_acc1, 0));
   HIPCHK(launch_msm_reduce(h->plan, S.workspace, S.d_result_jac, S.d_out_abi, st));
-  HIPCHK(hipMemcpyAsync(S.h_out, S.d_out_abi, grp_pt_bytes(h->grp), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(S.h_out, S.d_out_abi, abi_pt_bytes(h->grp), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(S.e_done, st));
   S.busy = true;
   return ZKT_OK;
@@ -653,7 +622,7 @@ static int msm_collect_locked(zkt_bases_impl* h, int slot, void* out, uint32_t* 
     HIPCHK(hipMemcpyAsync(dev_partial_jac, S.d_result_jac, 3 * grp_coord_bytes(h->grp), hipMemcpyDeviceToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
   }
-  if (out) memcpy(out, S.h_out, grp_pt_bytes(h->grp));
+  if (out) memcpy(out, S.h_out, abi_pt_bytes(h->grp));
   float ms = 0.f;
   if (S.timed && hipEventElapsedTime(&ms, S.e_acc0, S.e_acc1) == hipSuccess) { t_kernel_ms = ms; t_kernel_name = "k_accumulate"; }
   else { t_kernel_ms = 0.f; t_kernel_name = "msm_graph"; }      // a graph-replayed MSM carries no per-kernel events: say so instead of leaving the previous operation's figures
@@ -712,7 +681,7 @@ int zkt_internal_jac_sum(int grp, const uint32_t* dev_partials, size_t count, si
   if (!dev_partials || !out || count == 0) return ZKT_ERR_SHAPE;
   std::lock_guard<std::mutex> lk(g.mu);
   HIPCHK(launch_msm_jac_sum_to_affine(grp, dev_partials, count, stride_words, g.d_small, s));
-  HIPCHK(hipMemcpyAsync(out, g.d_small, grp_pt_bytes(grp), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(out, g.d_small, abi_pt_bytes(grp), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return ZKT_OK;
 }
@@ -725,9 +694,9 @@ static int jac_sum_dev(int grp, const uint32_t* dev_partials, size_t count, void
 static int msm_host(int grp, const void* bases, const uint64_t* scalars, size_t n, void* out) {
   if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
   if (!out || (n && (!bases || !scalars)) || n >= (size_t(1) << 26)) return ZKT_ERR_SHAPE;      // entry offsets are 32-bit: nwin * n < 2^32
-  if (n == 0) { memset(out, 0, grp_pt_bytes(grp)); ((uint32_t*)out)[grp_pt_bytes(grp) / 4 - 2] = 1; return ZKT_OK; }
+  if (n == 0) { memset(out, 0, abi_pt_bytes(grp)); ((uint32_t*)out)[abi_pt_bytes(grp) / 4 - 2] = 1; return ZKT_OK; }
   const MsmPlan plan = msm_plan_direct(n, grp);
-  const size_t ptb = grp_pt_bytes(grp), cb = grp_coord_bytes(grp);
+  const size_t ptb = abi_pt_bytes(grp), cb = grp_coord_bytes(grp);
   uint8_t* blob = nullptr;                                   // [abi points | scalars | kernel-layout points | inf flags | jac | abi out | workspace]
   const size_t o_abi = 0, o_sc = padded(n * ptb), o_tab = o_sc + padded(n * 32), o_inf = o_tab + padded(n * 2 * cb), o_jac = o_inf + padded(n),
                o_out = o_jac + padded(4 * cb), o_ws = o_out + padded(ptb), total = o_ws + plan.ws_bytes;

@@ -25,10 +25,7 @@
 #include <cstdlib>
 #include "../../include/zkt.h"
 #include "zkt_internal.h"
-
-extern int zkt_internal_ready();                 // zkt_api.cpp: ready + hipSetDevice(the library's device)
-extern hipStream_t zkt_internal_stream();
-extern "C" int zkt_internal_jac_sum(int grp, const uint32_t* dev_partials, size_t count, size_t stride_words, hipStream_t s, void* out);
+#include "host_abi.h"
 
 namespace {
 // ---- RCCL, bound at run time ------------------------------------------------------------------------------------------------------
@@ -80,7 +77,6 @@ constexpr size_t HDR_WORDS = 2;                               // status word (+ 
 constexpr size_t SLOT_WORDS = PAYLOAD_WORDS + HDR_WORDS;
 constexpr uint32_t STATUS_UNSET = 0xffffffffu;                // what a send slot holds between exchanges: a rank that could not even upload its status reads as failed everywhere
 
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[zkt] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return ZKT_ERR_DEVICE; } } while (0)
 #define NCCLCHK(x) do { ncclResult_t _r = (x); if (_r != ncclSuccess) { fprintf(stderr, "[zkt] RCCL error %s at %s:%d\n", rccl.GetErrorString(_r), __FILE__, __LINE__); return ZKT_ERR_DEVICE; } } while (0)
 
 void release_locked() {

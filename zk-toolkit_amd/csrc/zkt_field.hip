@@ -8,7 +8,6 @@
 namespace zkt {
 
 static constexpr int TPB = 256;
-static inline unsigned nblocks(size_t n, int tpb = TPB) { return (unsigned)((n + tpb - 1) / tpb); }
 
 template <class C, int OP>
 __global__ void __launch_bounds__(TPB) k_fp_op(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
@@ -51,7 +50,7 @@ __global__ void __launch_bounds__(TPB) k_fp_op(const uint32_t* __restrict__ a, c
 template <class C>
 static hipError_t launch_fp_c(int op, const uint32_t* a, const uint32_t* b, uint32_t* o, size_t n, unsigned long long* err, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  dim3 g(nblocks(n)), t(TPB);
+  dim3 g(grid_blocks(n)), t(TPB);
   switch (op) {
     case OP_ADD: hipLaunchKernelGGL((k_fp_op<C, OP_ADD>), g, t, 0, s, a, b, o, n, err); break;
     case OP_SUB: hipLaunchKernelGGL((k_fp_op<C, OP_SUB>), g, t, 0, s, a, b, o, n, err); break;
@@ -95,7 +94,7 @@ __global__ void __launch_bounds__(TPB) k_fp_pow_seq(const uint32_t* __restrict__
 }
 hipError_t launch_fp_pow(int field, const uint32_t* a, const uint32_t* e, int e_words, bool shared, uint32_t* o, size_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  dim3 g(nblocks(n)), t(TPB);
+  dim3 g(grid_blocks(n)), t(TPB);
   switch (field) {
     case F_FQ: hipLaunchKernelGGL(k_fp_pow<FqC>, g, t, 0, s, a, e, e_words, shared ? 1 : 0, o, n); break;
     case F_FR: hipLaunchKernelGGL(k_fp_pow<FrC>, g, t, 0, s, a, e, e_words, shared ? 1 : 0, o, n); break;
@@ -107,7 +106,7 @@ hipError_t launch_fp_pow(int field, const uint32_t* a, const uint32_t* e, int e_
 }
 hipError_t launch_fp_pow_seq(int field, const uint32_t* base, uint32_t* o, size_t n, bool repeat, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  dim3 g(nblocks(n)), t(TPB);
+  dim3 g(grid_blocks(n)), t(TPB);
   switch (field) {
     case F_FQ: hipLaunchKernelGGL(k_fp_pow_seq<FqC>, g, t, 0, s, base, o, n, repeat ? 1 : 0); break;
     case F_FR: hipLaunchKernelGGL(k_fp_pow_seq<FrC>, g, t, 0, s, base, o, n, repeat ? 1 : 0); break;
@@ -145,7 +144,7 @@ __global__ void __launch_bounds__(TPB) k_fp_sum(const uint32_t* __restrict__ a, 
   if (t == 0) st_fp<C>(out + (size_t)blockIdx.x * A, acc);
 }
 template <class C> static hipError_t sum_c(const uint32_t* a, size_t n, uint32_t* o, uint32_t* parts, hipStream_t s) {
-  const unsigned nb = (unsigned)(nblocks(n) < (unsigned)SUM_MAX_BLOCKS ? nblocks(n) : SUM_MAX_BLOCKS);
+  const unsigned nb = (unsigned)(grid_blocks(n) < (unsigned)SUM_MAX_BLOCKS ? grid_blocks(n) : SUM_MAX_BLOCKS);
   if (nb <= 1) { hipLaunchKernelGGL(k_fp_sum<C>, dim3(1), dim3(TPB), 0, s, a, n, o); return hipGetLastError(); }
   hipLaunchKernelGGL(k_fp_sum<C>, dim3(nb), dim3(TPB), 0, s, a, n, parts);
   hipLaunchKernelGGL(k_fp_sum<C>, dim3(1), dim3(TPB), 0, s, (const uint32_t*)parts, (size_t)nb, o);
@@ -163,7 +162,7 @@ hipError_t launch_fp_sum(int field, const uint32_t* a, size_t n, uint32_t* o, ui
 }
 hipError_t launch_fp_scale(int field, const uint32_t* a, const uint32_t* k, uint32_t* o, size_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  dim3 g(nblocks(n)), t(TPB);
+  dim3 g(grid_blocks(n)), t(TPB);
   switch (field) {
     case F_FQ: hipLaunchKernelGGL(k_fp_scale<FqC>, g, t, 0, s, a, k, o, n); break;
     case F_FR: hipLaunchKernelGGL(k_fp_scale<FrC>, g, t, 0, s, a, k, o, n); break;
@@ -183,7 +182,7 @@ __global__ void __launch_bounds__(64) k_selftest_fq_program(unsigned long long s
 }
 hipError_t launch_selftest_fq_program(unsigned long long seed0, int steps, const uint32_t* in4, uint32_t* out4, int* bad, size_t count, hipStream_t s) {
   if (count == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_selftest_fq_program, dim3(nblocks(count, 64)), dim3(64), 0, s, seed0, steps, in4, out4, bad, count);
+  hipLaunchKernelGGL(k_selftest_fq_program, dim3(grid_blocks(count, 64)), dim3(64), 0, s, seed0, steps, in4, out4, bad, count);
   return hipGetLastError();
 }
 
@@ -233,7 +232,7 @@ __global__ void __launch_bounds__(64) k_tower_op(int op, const uint32_t* __restr
 }
 hipError_t launch_tower_op(int deg, int op, const uint32_t* a, const uint32_t* b, uint32_t* o, size_t n, unsigned long long* err, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  dim3 g(nblocks(n, 64)), t(64);
+  dim3 g(grid_blocks(n, 64)), t(64);
   if (deg == 2) hipLaunchKernelGGL(k_tower_op<2>, g, t, 0, s, op, a, b, o, n, err);
   else if (deg == 6) hipLaunchKernelGGL(k_tower_op<6>, g, t, 0, s, op, a, b, o, n, err);
   else if (deg == 12) { if (op == T_REDUCE) return hipErrorInvalidValue; hipLaunchKernelGGL(k_tower_op<12>, g, t, 0, s, op, a, b, o, n, err); }
@@ -250,7 +249,7 @@ __global__ void __launch_bounds__(64) k_fq12_pow(const uint32_t* __restrict__ a,
 }
 hipError_t launch_fq12_pow(const uint32_t* a, const uint32_t* e, int nl, uint32_t* o, size_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_fq12_pow, dim3(nblocks(n, 64)), dim3(64), 0, s, a, e, nl, o, n);
+  hipLaunchKernelGGL(k_fq12_pow, dim3(grid_blocks(n, 64)), dim3(64), 0, s, a, e, nl, o, n);
   return hipGetLastError();
 }
 

@@ -34,6 +34,7 @@
 #include "abi.h"
 #include "zkt_internal.h"
 #include "../../include/zkt.h"
+#include "host_abi.h"
 
 namespace zkt {
 typedef FrC C;
@@ -305,39 +306,20 @@ __global__ void __launch_bounds__(256) k_prove_scalars(const uint32_t* __restric
 using namespace zkt;
 
 namespace {
-#define RCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[zkt] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return ZKT_ERR_DEVICE; } } while (0)
-#define ZCHK(x) do { int _rc = (x); if (_rc != ZKT_OK) return _rc; } while (0)
-inline unsigned nb(size_t n) { return (unsigned)((n + 255) / 256); }
-const size_t G1B = sizeof(zkt_g1_affine), G2B = sizeof(zkt_g2_affine), FRB = 32;
-const uint64_t G1_GEN[13] = {0xfb3af00adb22c6bbull, 0x6c55e83ff97a1aefull, 0xa14e3a3f171bac58ull, 0xc3688c4f9774b905ull, 0x2695638c4fa9ac0full, 0x17f1d3a73197d794ull,
-                             0x0caa232946c5e7e1ull, 0xd03cc744a2888ae4ull, 0x00db18cb2c04b3edull, 0xfcf5e095d5d00af6ull, 0xa09e30ed741d8ae4ull, 0x08b3f481e3aaa0f1ull, 0};   // g1_point.rs:38-47
-const uint64_t G2_GEN[25] = {0xe5ac7d055d042b7eull, 0x334cf11213945d57ull, 0xb5da61bbdc7f5049ull, 0x596bd0d09920b61aull, 0x7dacd3a088274f65ull, 0x13e02b6052719f60ull,
-                             0xd48056c8c121bdb8ull, 0x0bac0326a805bbefull, 0xb4510b647ae3d177ull, 0xc6e47ad4fa403b02ull, 0x260805272dc51051ull, 0x024aa2b2f08f0a91ull,
-                             0xaaa9075ff05f79beull, 0x3f370d275cec1da1ull, 0x267492ab572e99abull, 0xcb3e287e85a763afull, 0x32acd2b02bc28b99ull, 0x0606c4a02ea734ccull,
-                             0xe193548608b82801ull, 0x923ac9cc3baca289ull, 0x6d429a695160d12cull, 0xadfd9baa8cbdd3a7ull, 0x8cc9cdc6da2e351aull, 0x0ce5d527727d6e11ull, 0};   // g2_point.rs:36-46
-
-struct DBuf {                       // owning device buffer
-  void* p = nullptr; size_t bytes = 0;
-  int alloc(size_t b) { bytes = b ? b : 32; return hipMalloc(&p, bytes) == hipSuccess ? ZKT_OK : ZKT_ERR_DEVICE; }
-  void release() { if (p) hipFree(p); p = nullptr; }
-  ~DBuf() { release(); }
-  uint32_t* w() const { return (uint32_t*)p; }
-  DBuf() = default; DBuf(const DBuf&) = delete; DBuf& operator=(const DBuf&) = delete;
-};
-struct Csr { DBuf ptr, idx, val, long_rows; size_t rows = 0, nnz = 0, n_long = 0; };
+struct Csr { Dev ptr, idx, val, long_rows; size_t rows = 0, nnz = 0, n_long = 0; };
 
 // inclusive prefix product, in place allowed (in == out); two levels of tiles cover 2048^2 elements
 int scan_mul(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) {
   if (n == 0) return ZKT_OK;
   const size_t tiles = (n + SC_TILE - 1) / SC_TILE;
   if (tiles > (size_t)SC_TILE) return ZKT_ERR_SHAPE;
-  DBuf tot, tot2; ZCHK(tot.alloc(tiles * FRB)); ZCHK(tot2.alloc(FRB));
+  Dev tot, tot2; ZCHK(tot.alloc(tiles * FRB)); ZCHK(tot2.alloc(FRB));
   hipLaunchKernelGGL(k_scanmul_tile, dim3((unsigned)tiles), dim3(SC_TPB), 0, s, in, out, n, tot.w());
   if (tiles > 1) {
     hipLaunchKernelGGL(k_scanmul_tile, dim3(1), dim3(SC_TPB), 0, s, (const uint32_t*)tot.w(), tot.w(), tiles, tot2.w());
-    hipLaunchKernelGGL(k_scanmul_apply, dim3(nb(n)), dim3(256), 0, s, out, n, (const uint32_t*)tot.w());
+    hipLaunchKernelGGL(k_scanmul_apply, dim3(grid_blocks(n)), dim3(256), 0, s, out, n, (const uint32_t*)tot.w());
   }
-  RCHK(hipStreamSynchronize(s));     // the tile totals die with this frame
+  HIPCHK(hipStreamSynchronize(s));     // the tile totals die with this frame
   return ZKT_OK;
 }
 // stage groups: the contiguous one first (distances 1..2^(c0-1)), then strided groups of <= 8 stages with >= 4 adjacent columns
@@ -357,17 +339,17 @@ int ntt_forward(uint32_t* a, int logN, const uint32_t* tw, const uint32_t* mulve
   for (int i = k - 1; i >= 0; --i)
     hipLaunchKernelGGL(k_ntt_group<true>, dim3((unsigned)((batch << logN) >> (g[i].cnt + g[i].cbits)), ny), dim3(NTT_TPB), 0, s, a, logN, g[i].lo, g[i].cnt, g[i].cbits, tw,
                        i == 0 ? mulvec : (const uint32_t*)nullptr, ystride);
-  RCHK(hipGetLastError()); return ZKT_OK;
+  HIPCHK(hipGetLastError()); return ZKT_OK;
 }
 int ntt_inverse(uint32_t* a, int logN, const uint32_t* twinv, hipStream_t s, size_t batch = 1, unsigned ny = 1, size_t ystride = 0) {
   NttGroup g[8]; const int k = ntt_groups(logN, g);
   for (int i = 0; i < k; ++i)
     hipLaunchKernelGGL(k_ntt_group<false>, dim3((unsigned)((batch << logN) >> (g[i].cnt + g[i].cbits)), ny), dim3(NTT_TPB), 0, s, a, logN, g[i].lo, g[i].cnt, g[i].cbits, twinv,
                        (const uint32_t*)nullptr, ystride);
-  RCHK(hipGetLastError()); return ZKT_OK;
+  HIPCHK(hipGetLastError()); return ZKT_OK;
 }
 void spmv(const Csr& M, const uint32_t* vec, uint32_t* out, hipStream_t s) {
-  hipLaunchKernelGGL(k_spmv, dim3(nb(M.rows)), dim3(256), 0, s, (const uint32_t*)M.ptr.w(), (const uint32_t*)M.idx.w(), (const uint32_t*)M.val.w(), vec, out, M.rows);
+  hipLaunchKernelGGL(k_spmv, dim3(grid_blocks(M.rows)), dim3(256), 0, s, (const uint32_t*)M.ptr.w(), (const uint32_t*)M.idx.w(), (const uint32_t*)M.val.w(), vec, out, M.rows);
   if (M.n_long) hipLaunchKernelGGL(k_spmv_long, dim3((unsigned)M.n_long), dim3(256), 0, s, (const uint32_t*)M.ptr.w(), (const uint32_t*)M.idx.w(), (const uint32_t*)M.val.w(), vec, out, (const uint32_t*)M.long_rows.w());
 }
 // host CSR (reference order: one sparse row per constraint, r1cs.rs / constraint.rs:5-9) -> device CSR and its transpose
@@ -387,15 +369,15 @@ int upload_csr(const zkt_sparse_rows* M, size_t n, size_t cols, Csr& rowwise, Cs
     std::vector<uint32_t> lr;
     for (size_t i = 0; i < rows; ++i) if (p[i + 1] - p[i] > SPMV_LONG) lr.push_back((uint32_t)i);
     c.n_long = lr.size();
-    if (c.n_long) { ZCHK(c.long_rows.alloc(lr.size() * 4)); RCHK(hipMemcpy(c.long_rows.p, lr.data(), lr.size() * 4, hipMemcpyHostToDevice)); }
+    if (c.n_long) { ZCHK(c.long_rows.alloc(lr.size() * 4)); HIPCHK(hipMemcpy(c.long_rows.p, lr.data(), lr.size() * 4, hipMemcpyHostToDevice)); }
     ZCHK(c.ptr.alloc(p.size() * 4)); ZCHK(c.idx.alloc(nnz * 4)); ZCHK(c.val.alloc(nnz * FRB));
-    RCHK(hipMemcpyAsync(c.ptr.p, p.data(), p.size() * 4, hipMemcpyHostToDevice, s));
+    ZCHK(up(c.ptr, p.data(), p.size() * 4, s));
     if (nnz) {
-      DBuf tmp; ZCHK(tmp.alloc(nnz * FRB));
-      RCHK(hipMemcpyAsync(c.idx.p, idx, nnz * 4, hipMemcpyHostToDevice, s));
-      RCHK(hipMemcpyAsync(tmp.p, val, nnz * FRB, hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(k_to_mont, dim3(nb(nnz)), dim3(256), 0, s, (const uint32_t*)tmp.w(), c.val.w(), nnz);
-      RCHK(hipStreamSynchronize(s));
+      Dev tmp; ZCHK(tmp.alloc(nnz * FRB));
+      ZCHK(up(c.idx, idx, nnz * 4, s));
+      ZCHK(up(tmp, val, nnz * FRB, s));
+      hipLaunchKernelGGL(k_to_mont, dim3(grid_blocks(nnz)), dim3(256), 0, s, (const uint32_t*)tmp.w(), c.val.w(), nnz);
+      HIPCHK(hipStreamSynchronize(s));
     }
     return ZKT_OK;
   };
@@ -410,16 +392,16 @@ struct zkt_groth16_pk {
   // the quotient's blocked convolution (k_recip_blocks): this rank's cnt = hiC2 - loC2 values h(n+s), s = qs0 .. qs0+cnt-1, from Q input blocks of Bi, transforms of size M = 2 Bi
   size_t qcnt = 0, qs0 = 1, Bi = 1, M = 2, Q = 1; int logM = 1;
   Csr A, B, Cm;                                  // constraint rows (device), values in Montgomery form
-  DBuf cinv, P, ghat, tw, twinv;                  // Fr tables
+  Dev cinv, P, ghat, tw, twinv;                  // Fr tables
   zkt_g1_bases *setA = nullptr, *setC1 = nullptr, *setC2 = nullptr; zkt_g2_bases* setB = nullptr;   // the resident base sets (see the file header)
   size_t nA = 0, nC1 = 0, nC2 = 0;
   size_t loA = 0, hiA = 0, loC1 = 0, hiC1 = 0, loC2 = 0, hiC2 = 0;     // this shard's index ranges of the A/B sets and of the two C sets (whole sets when unsharded)
-  DBuf cparts;                                   // the Jacobian partials of C1 and C2 of the proof being collected
+  Dev cparts;                                   // the Jacobian partials of C1 and C2 of the proof being collected
   size_t shard = 0, nshards = 1;
   // per-proof work buffers.  The MSM scalar vectors (and r, s) are double-buffered: proof k+1's Fr stage may run while the MSMs of proof k
   // are still reading theirs (zkt_groth16_prove_r1cs_submit / _collect); everything else is consumed in stream order before it is rewritten.
   static constexpr int PSLOTS = 2;
-  DBuf wires_c, wires_m, z_m[3], X, sA[PSLOTS], sB[PSLOTS], sC[PSLOTS], rs[PSLOTS];       // X[p][q][M]: the block spectra of a, b, c
+  Dev wires_c, wires_m, z_m[3], X, sA[PSLOTS], sB[PSLOTS], sC[PSLOTS], rs[PSLOTS];       // X[p][q][M]: the block spectra of a, b, c
   bool pending[PSLOTS] = {false, false};
   hipStream_t s = nullptr, sq = nullptr;        // the key's stream (head of the Fr stage, collection) and the quotient stage's own (three transform pairs; high priority)
   hipEvent_t e_head = nullptr, e_q = nullptr;   // (A w), (B w), (C w) and the scalar vectors are ready / the quotient stage has consumed them
@@ -433,9 +415,6 @@ struct zkt_groth16_pk {
   }
 };
 
-extern int zkt_internal_ready();   // zkt_api.cpp
-extern "C" int zkt_internal_bases_share_streams(void* dst, void* src, int share_acc, int tail_base, int tail_span);
-extern void zkt_internal_set_error_index(size_t i);
 
 extern "C" {
 
@@ -463,79 +442,79 @@ int zkt_groth16_setup_r1cs_sharded(size_t n, size_t l, size_t m, const zkt_spars
   int logM = 1; while (((size_t)1 << (logM - 1)) < pk->qcnt || (logM <= 10 && ((size_t)1 << (logM - 1)) < n)) ++logM;      // Bi >= cnt; not below min(n, 1024) (many ranks on a small circuit)
   const size_t M = (size_t)1 << logM, Bi = M / 2, Q = pk->qcnt ? (n + Bi - 1) / Bi : 1, QM = Q * M;
   pk->logM = logM; pk->M = M; pk->Bi = Bi; pk->Q = Q;
-  { int lo = 0, hi = 0; RCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    RCHK(hipStreamCreateWithFlags(&pk->s, hipStreamNonBlocking)); RCHK(hipStreamCreateWithPriority(&pk->sq, hipStreamNonBlocking, hi));
-    RCHK(hipEventCreateWithFlags(&pk->e_head, hipEventDisableTiming)); RCHK(hipEventCreateWithFlags(&pk->e_q, hipEventDisableTiming)); }
+  { int lo = 0, hi = 0; HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    HIPCHK(hipStreamCreateWithFlags(&pk->s, hipStreamNonBlocking)); HIPCHK(hipStreamCreateWithPriority(&pk->sq, hipStreamNonBlocking, hi));
+    HIPCHK(hipEventCreateWithFlags(&pk->e_head, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&pk->e_q, hipEventDisableTiming)); }
   hipStream_t s = pk->s;
   Csr At, Bt, Ct;
   ZCHK(upload_csr(A, n, rows, pk->A, At, s)); ZCHK(upload_csr(B, n, rows, pk->B, Bt, s)); ZCHK(upload_csr(Cmat, n, rows, pk->Cm, Ct, s));
 
   // ---- Fr tables ----
-  DBuf dtrap, consts, fact, invfact, xm, pre, xinv, Lm, Lc, hbc, derr;
+  Dev dtrap, consts, fact, invfact, xm, pre, xinv, Lm, Lc, hbc, derr;
   ZCHK(dtrap.alloc(160)); ZCHK(consts.alloc(K_COUNT * FRB)); ZCHK(fact.alloc((2 * n + 1) * FRB)); ZCHK(invfact.alloc((2 * n + 1) * FRB));
   ZCHK(xm.alloc((2 * n) * FRB)); ZCHK(pre.alloc((2 * n) * FRB)); ZCHK(xinv.alloc((2 * n) * FRB)); ZCHK(Lm.alloc(n * FRB)); ZCHK(Lc.alloc(n * FRB));
   ZCHK(hbc.alloc(n * FRB)); ZCHK(derr.alloc(8));
   ZCHK(pk->cinv.alloc(n * FRB)); ZCHK(pk->P.alloc(n * FRB)); ZCHK(pk->ghat.alloc(QM * FRB)); ZCHK(pk->tw.alloc(M / 2 * FRB)); ZCHK(pk->twinv.alloc(M / 2 * FRB));
   unsigned long long noerr = NO_ERR;
-  RCHK(hipMemcpyAsync(derr.p, &noerr, 8, hipMemcpyHostToDevice, s));
-  RCHK(hipMemcpyAsync(dtrap.p, trap, 160, hipMemcpyHostToDevice, s));
+  ZCHK(up(derr, &noerr, 8, s));
+  ZCHK(up(dtrap, trap, 160, s));
   hipLaunchKernelGGL(k_setup_consts, dim3(1), dim3(64), 0, s, (const uint32_t*)dtrap.w(), consts.w(), logM);
-  hipLaunchKernelGGL(k_iota, dim3(nb(2 * n + 1)), dim3(256), 0, s, fact.w(), 2 * n + 1);
+  hipLaunchKernelGGL(k_iota, dim3(grid_blocks(2 * n + 1)), dim3(256), 0, s, fact.w(), 2 * n + 1);
   ZCHK(scan_mul(fact.w(), fact.w(), 2 * n + 1, s));
-  hipLaunchKernelGGL(k_inv, dim3(nb(2 * n + 1)), dim3(256), 0, s, (const uint32_t*)fact.w(), invfact.w(), 2 * n + 1, (unsigned long long*)derr.p);
+  hipLaunchKernelGGL(k_inv, dim3(grid_blocks(2 * n + 1)), dim3(256), 0, s, (const uint32_t*)fact.w(), invfact.w(), 2 * n + 1, (unsigned long long*)derr.p);
   const size_t nx = 2 * n - 1;
-  hipLaunchKernelGGL(k_x_minus, dim3(nb(nx)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_X * FW), xm.w(), nx);
+  hipLaunchKernelGGL(k_x_minus, dim3(grid_blocks(nx)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_X * FW), xm.w(), nx);
   ZCHK(scan_mul(xm.w(), pre.w(), nx, s));
-  hipLaunchKernelGGL(k_inv, dim3(nb(nx)), dim3(256), 0, s, (const uint32_t*)xm.w(), xinv.w(), nx, (unsigned long long*)derr.p);
+  hipLaunchKernelGGL(k_inv, dim3(grid_blocks(nx)), dim3(256), 0, s, (const uint32_t*)xm.w(), xinv.w(), nx, (unsigned long long*)derr.p);
   unsigned long long e = NO_ERR;
-  RCHK(hipMemcpyAsync(&e, derr.p, 8, hipMemcpyDeviceToHost, s)); RCHK(hipStreamSynchronize(s));
+  ZCHK(down(&e, derr.p, 8, s)); HIPCHK(hipStreamSynchronize(s));
   if (e != NO_ERR) { zkt_internal_set_error_index((size_t)e); return ZKT_ERR_INV_ZERO; }      // x fell on the domain {1..2n-1}: t(x) = 0, no CRS
   hipLaunchKernelGGL(k_setup_consts2, dim3(1), dim3(64), 0, s, (const uint32_t*)pre.w(), n, consts.w());
-  hipLaunchKernelGGL(k_lagrange, dim3(nb(n)), dim3(256), 0, s, (const uint32_t*)consts.w(), (const uint32_t*)invfact.w(), (const uint32_t*)xinv.w(), n, pk->cinv.w(), Lm.w(), Lc.w());
-  if (n >= 2) hipLaunchKernelGGL(k_hbasis, dim3(nb(n - 1)), dim3(256), 0, s, (const uint32_t*)consts.w(), (const uint32_t*)fact.w(), (const uint32_t*)invfact.w(), (const uint32_t*)xinv.w(), n, hbc.w(), pk->P.w());
+  hipLaunchKernelGGL(k_lagrange, dim3(grid_blocks(n)), dim3(256), 0, s, (const uint32_t*)consts.w(), (const uint32_t*)invfact.w(), (const uint32_t*)xinv.w(), n, pk->cinv.w(), Lm.w(), Lc.w());
+  if (n >= 2) hipLaunchKernelGGL(k_hbasis, dim3(grid_blocks(n - 1)), dim3(256), 0, s, (const uint32_t*)consts.w(), (const uint32_t*)fact.w(), (const uint32_t*)invfact.w(), (const uint32_t*)xinv.w(), n, hbc.w(), pk->P.w());
   // twiddles: w^k and w^-k, k < M/2, as prefix products
-  hipLaunchKernelGGL(k_fill_pow, dim3(nb(M / 2)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_OMEGA * FW), pk->tw.w(), M / 2);
+  hipLaunchKernelGGL(k_fill_pow, dim3(grid_blocks(M / 2)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_OMEGA * FW), pk->tw.w(), M / 2);
   ZCHK(scan_mul(pk->tw.w(), pk->tw.w(), M / 2, s));
-  hipLaunchKernelGGL(k_fill_pow, dim3(nb(M / 2)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_OMEGA_INV * FW), pk->twinv.w(), M / 2);
+  hipLaunchKernelGGL(k_fill_pow, dim3(grid_blocks(M / 2)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_OMEGA_INV * FW), pk->twinv.w(), M / 2);
   ZCHK(scan_mul(pk->twinv.w(), pk->twinv.w(), M / 2, s));
   // the Q kernel slices of this rank and their spectra (with the 1/M of the inverse transform)
-  hipLaunchKernelGGL(k_recip_blocks, dim3(nb(QM)), dim3(256), 0, s, (const uint32_t*)fact.w(), (const uint32_t*)invfact.w(), n, pk->qs0, pk->qcnt, Bi, Q, pk->ghat.w());
+  hipLaunchKernelGGL(k_recip_blocks, dim3(grid_blocks(QM)), dim3(256), 0, s, (const uint32_t*)fact.w(), (const uint32_t*)invfact.w(), n, pk->qs0, pk->qcnt, Bi, Q, pk->ghat.w());
   ZCHK(ntt_forward(pk->ghat.w(), logM, pk->tw.w(), nullptr, s, Q));
-  hipLaunchKernelGGL(k_scale_all, dim3(nb(QM)), dim3(256), 0, s, pk->ghat.w(), (const uint32_t*)(consts.w() + K_NINV * FW), QM);
+  hipLaunchKernelGGL(k_scale_all, dim3(grid_blocks(QM)), dim3(256), 0, s, pk->ghat.w(), (const uint32_t*)(consts.w() + K_NINV * FW), QM);
 
   // ---- per-wire evaluations u_i(x) = sum_j A[j][i] L_j(x)  and the scalars of crs.rs:66-84 ----
-  DBuf ue, ve, we, y; ZCHK(ue.alloc(rows * FRB)); ZCHK(ve.alloc(rows * FRB)); ZCHK(we.alloc(rows * FRB)); ZCHK(y.alloc(rows * FRB));
-  Csr* T[3] = {&At, &Bt, &Ct}; DBuf* ev[3] = {&ue, &ve, &we};
+  Dev ue, ve, we, y; ZCHK(ue.alloc(rows * FRB)); ZCHK(ve.alloc(rows * FRB)); ZCHK(we.alloc(rows * FRB)); ZCHK(y.alloc(rows * FRB));
+  Csr* T[3] = {&At, &Bt, &Ct}; Dev* ev[3] = {&ue, &ve, &we};
   for (int k = 0; k < 3; ++k) spmv(*T[k], Lm.w(), ev[k]->w(), s);
-  hipLaunchKernelGGL(k_uvw, dim3(nb(rows)), dim3(256), 0, s, (const uint32_t*)consts.w(), (const uint32_t*)ue.w(), (const uint32_t*)ve.w(), (const uint32_t*)we.w(), l, rows, y.w());
-  RCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_uvw, dim3(grid_blocks(rows)), dim3(256), 0, s, (const uint32_t*)consts.w(), (const uint32_t*)ue.w(), (const uint32_t*)ve.w(), (const uint32_t*)we.w(), l, rows, y.w());
+  HIPCHK(hipGetLastError());
 
   // ---- group side: fixed-base multiplications of the generators (crs.rs:85-135), written straight into the three base sets ----
-  DBuf gen1, gen2, pU, pA, pB, pC, small1, small2, gt;
+  Dev gen1, gen2, pU, pA, pB, pC, small1, small2, gt;
   ZCHK(gen1.alloc(G1B)); ZCHK(gen2.alloc(G2B)); ZCHK(pU.alloc(rows * G1B)); ZCHK(pA.alloc(nA * G1B)); ZCHK(pB.alloc(nA * G2B)); ZCHK(pC.alloc(nC * G1B));
   ZCHK(small1.alloc(3 * G1B)); ZCHK(small2.alloc(3 * G2B)); ZCHK(gt.alloc(576));
-  RCHK(hipMemcpyAsync(gen1.p, G1_GEN, G1B, hipMemcpyHostToDevice, s)); RCHK(hipMemcpyAsync(gen2.p, G2_GEN, G2B, hipMemcpyHostToDevice, s));
-  RCHK(launch_generator_mul(G_G1, gen1.w(), dtrap.w(), small1.w(), 1, s));               // alpha
-  RCHK(launch_generator_mul(G_G1, gen1.w(), dtrap.w() + 8, small1.w() + 26, 1, s));      // beta
-  RCHK(launch_generator_mul(G_G1, gen1.w(), dtrap.w() + 24, small1.w() + 52, 1, s));     // delta
-  RCHK(launch_generator_mul(G_G2, gen2.w(), dtrap.w() + 8, small2.w(), 1, s));           // beta
-  RCHK(launch_generator_mul(G_G2, gen2.w(), dtrap.w() + 16, small2.w() + 50, 1, s));     // gamma
-  RCHK(launch_generator_mul(G_G2, gen2.w(), dtrap.w() + 24, small2.w() + 100, 1, s));    // delta
+  ZCHK(up(gen1, &G1_GEN, G1B, s)); ZCHK(up(gen2, &G2_GEN, G2B, s));
+  HIPCHK(launch_generator_mul(G_G1, gen1.w(), dtrap.w(), small1.w(), 1, s));               // alpha
+  HIPCHK(launch_generator_mul(G_G1, gen1.w(), dtrap.w() + 8, small1.w() + 26, 1, s));      // beta
+  HIPCHK(launch_generator_mul(G_G1, gen1.w(), dtrap.w() + 24, small1.w() + 52, 1, s));     // delta
+  HIPCHK(launch_generator_mul(G_G2, gen2.w(), dtrap.w() + 8, small2.w(), 1, s));           // beta
+  HIPCHK(launch_generator_mul(G_G2, gen2.w(), dtrap.w() + 16, small2.w() + 50, 1, s));     // gamma
+  HIPCHK(launch_generator_mul(G_G2, gen2.w(), dtrap.w() + 24, small2.w() + 100, 1, s));    // delta
   // uvw: statement part to the verifying key, witness part into the C1 set.  pC = [L (n) | uvw_wit (nw) | alpha, beta, delta || Lambda t/delta (nh)]
-  RCHK(launch_generator_mul(G_G1, gen1.w(), y.w(), pU.w(), rows, s));
-  RCHK(hipMemcpyAsync(vk->g1_uvw_stmt, pU.p, (l + 1) * G1B, hipMemcpyDeviceToHost, s));
-  if (vk->g1_uvw_wit && nw) RCHK(hipMemcpyAsync(vk->g1_uvw_wit, pU.w() + (l + 1) * 26, nw * G1B, hipMemcpyDeviceToHost, s));
-  if (nw) RCHK(hipMemcpyAsync(pC.w() + n * 26, pU.w() + (l + 1) * 26, nw * G1B, hipMemcpyDeviceToDevice, s));
-  RCHK(launch_generator_mul(G_G1, gen1.w(), Lc.w(), pC.w(), n, s));                       // [L_j(x)]_1
-  RCHK(hipMemcpyAsync(pA.p, pC.p, n * G1B, hipMemcpyDeviceToDevice, s));
-  if (nh) RCHK(launch_generator_mul(G_G1, gen1.w(), hbc.w(), pC.w() + nC1 * 26, nh, s));        // [Lambda_s(x) t(x)/delta]_1
-  RCHK(launch_generator_mul(G_G2, gen2.w(), Lc.w(), pB.w(), n, s));                       // [L_j(x)]_2
-  RCHK(hipMemcpyAsync(pA.w() + n * 26, small1.p, G1B, hipMemcpyDeviceToDevice, s));            // A tail: alpha, delta
-  RCHK(hipMemcpyAsync(pA.w() + (n + 1) * 26, small1.w() + 52, G1B, hipMemcpyDeviceToDevice, s));
-  RCHK(hipMemcpyAsync(pB.w() + n * 50, small2.p, G2B, hipMemcpyDeviceToDevice, s));            // B tail: beta, delta
-  RCHK(hipMemcpyAsync(pB.w() + (n + 1) * 50, small2.w() + 100, G2B, hipMemcpyDeviceToDevice, s));
-  RCHK(hipMemcpyAsync(pC.w() + (n + nw) * 26, small1.p, 3 * G1B, hipMemcpyDeviceToDevice, s));         // C1 tail: alpha, beta, delta
-  RCHK(hipStreamSynchronize(s));
+  HIPCHK(launch_generator_mul(G_G1, gen1.w(), y.w(), pU.w(), rows, s));
+  ZCHK(down(vk->g1_uvw_stmt, pU.p, (l + 1) * G1B, s));
+  if (vk->g1_uvw_wit && nw) ZCHK(down(vk->g1_uvw_wit, pU.w() + (l + 1) * 26, nw * G1B, s));
+  if (nw) HIPCHK(hipMemcpyAsync(pC.w() + n * 26, pU.w() + (l + 1) * 26, nw * G1B, hipMemcpyDeviceToDevice, s));
+  HIPCHK(launch_generator_mul(G_G1, gen1.w(), Lc.w(), pC.w(), n, s));                       // [L_j(x)]_1
+  HIPCHK(hipMemcpyAsync(pA.p, pC.p, n * G1B, hipMemcpyDeviceToDevice, s));
+  if (nh) HIPCHK(launch_generator_mul(G_G1, gen1.w(), hbc.w(), pC.w() + nC1 * 26, nh, s));        // [Lambda_s(x) t(x)/delta]_1
+  HIPCHK(launch_generator_mul(G_G2, gen2.w(), Lc.w(), pB.w(), n, s));                       // [L_j(x)]_2
+  HIPCHK(hipMemcpyAsync(pA.w() + n * 26, small1.p, G1B, hipMemcpyDeviceToDevice, s));            // A tail: alpha, delta
+  HIPCHK(hipMemcpyAsync(pA.w() + (n + 1) * 26, small1.w() + 52, G1B, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(pB.w() + n * 50, small2.p, G2B, hipMemcpyDeviceToDevice, s));            // B tail: beta, delta
+  HIPCHK(hipMemcpyAsync(pB.w() + (n + 1) * 50, small2.w() + 100, G2B, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(pC.w() + (n + nw) * 26, small1.p, 3 * G1B, hipMemcpyDeviceToDevice, s));         // C1 tail: alpha, beta, delta
+  HIPCHK(hipStreamSynchronize(s));
   pU.release();
   ZCHK(zkt_g1_bases_from_device((const zkt_g1_affine*)(pA.w() + pk->loA * 26), pk->hiA - pk->loA, s, &pk->setA)); pA.release();
   ZCHK(zkt_g2_bases_from_device((const zkt_g2_affine*)(pB.w() + pk->loA * 50), pk->hiA - pk->loA, s, &pk->setB)); pB.release();
@@ -556,13 +535,13 @@ int zkt_groth16_setup_r1cs_sharded(size_t n, size_t l, size_t m, const zkt_spars
     ZCHK(zkt_internal_bases_share_streams(pk->setC1, pk->setA, 1, 0, 2)); ZCHK(zkt_internal_bases_share_streams(pk->setC2, pk->setA, 1, 0, 2));
     ZCHK(zkt_internal_bases_share_streams(pk->setB, pk->setA, 0, 2, 2));
   }
-  RCHK(hipMemcpyAsync(derr.p, &noerr, 8, hipMemcpyHostToDevice, s));
-  RCHK(launch_tate(small1.w(), small2.w(), gt.w(), 1, (unsigned long long*)derr.p, s));        // crs.rs:137-139
-  RCHK(hipMemcpyAsync(vk->g1_alpha, small1.p, G1B, hipMemcpyDeviceToHost, s)); RCHK(hipMemcpyAsync(vk->g1_beta, small1.w() + 26, G1B, hipMemcpyDeviceToHost, s));
-  RCHK(hipMemcpyAsync(vk->g1_delta, small1.w() + 52, G1B, hipMemcpyDeviceToHost, s)); RCHK(hipMemcpyAsync(vk->g2_beta, small2.p, G2B, hipMemcpyDeviceToHost, s));
-  RCHK(hipMemcpyAsync(vk->g2_gamma, small2.w() + 50, G2B, hipMemcpyDeviceToHost, s)); RCHK(hipMemcpyAsync(vk->g2_delta, small2.w() + 100, G2B, hipMemcpyDeviceToHost, s));
-  RCHK(hipMemcpyAsync(vk->gt_alpha_beta, gt.p, 576, hipMemcpyDeviceToHost, s));
-  RCHK(hipStreamSynchronize(s));
+  ZCHK(up(derr, &noerr, 8, s));
+  HIPCHK(launch_tate(small1.w(), small2.w(), gt.w(), 1, (unsigned long long*)derr.p, s));        // crs.rs:137-139
+  ZCHK(down(vk->g1_alpha, small1.p, G1B, s)); ZCHK(down(vk->g1_beta, small1.w() + 26, G1B, s));
+  ZCHK(down(vk->g1_delta, small1.w() + 52, G1B, s)); ZCHK(down(vk->g2_beta, small2.p, G2B, s));
+  ZCHK(down(vk->g2_gamma, small2.w() + 50, G2B, s)); ZCHK(down(vk->g2_delta, small2.w() + 100, G2B, s));
+  ZCHK(down(vk->gt_alpha_beta, gt.p, 576, s));
+  HIPCHK(hipStreamSynchronize(s));
   vk->n = n; vk->l = l; vk->m = m;
 
   // ---- per-proof work buffers ----
@@ -591,17 +570,17 @@ static int prove_submit(zkt_groth16_pk* pk, int ps, const uint64_t* wires, bool 
   if (!wires || !r || !s_ || ps < 0 || ps >= zkt_groth16_pk::PSLOTS || pk->pending[ps]) return ZKT_ERR_SHAPE;
   const size_t n = pk->n, l = pk->l, m = pk->m, rows = m + 1, nw = m - l;
   hipStream_t s = pk->s;
-  DBuf &sA = pk->sA[ps], &sB = pk->sB[ps], &sC = pk->sC[ps], &drs = pk->rs[ps];
+  Dev &sA = pk->sA[ps], &sB = pk->sB[ps], &sC = pk->sC[ps], &drs = pk->rs[ps];
   uint64_t rs[8]; memcpy(rs, r, 32); memcpy(rs + 4, s_, 32);
-  RCHK(hipStreamWaitEvent(s, pk->e_q, 0));        // z_m and X are shared by the proof slots: the previous proof's quotient stage has to be through with them
-  RCHK(hipMemcpyAsync(drs.p, rs, 64, hipMemcpyHostToDevice, s));
-  RCHK(hipMemcpyAsync(pk->wires_c.p, wires, rows * FRB, wires_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_to_mont, dim3(nb(rows)), dim3(256), 0, s, (const uint32_t*)pk->wires_c.w(), pk->wires_m.w(), rows);
+  HIPCHK(hipStreamWaitEvent(s, pk->e_q, 0));        // z_m and X are shared by the proof slots: the previous proof's quotient stage has to be through with them
+  ZCHK(up(drs, rs, 64, s));
+  HIPCHK(hipMemcpyAsync(pk->wires_c.p, wires, rows * FRB, wires_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_to_mont, dim3(grid_blocks(rows)), dim3(256), 0, s, (const uint32_t*)pk->wires_c.w(), pk->wires_m.w(), rows);
   Csr* M[3] = {&pk->A, &pk->B, &pk->Cm};
   for (int k = 0; k < 3; ++k) spmv(*M[k], pk->wires_m.w(), pk->z_m[k].w(), s);
-  hipLaunchKernelGGL(k_prove_scalars, dim3(nb(n + nw + 1)), dim3(256), 0, s, (const uint32_t*)pk->z_m[0].w(), (const uint32_t*)pk->z_m[1].w(), (const uint32_t*)pk->wires_c.w(),
+  hipLaunchKernelGGL(k_prove_scalars, dim3(grid_blocks(n + nw + 1)), dim3(256), 0, s, (const uint32_t*)pk->z_m[0].w(), (const uint32_t*)pk->z_m[1].w(), (const uint32_t*)pk->wires_c.w(),
                      (const uint32_t*)drs.w(), n, l, m, sA.w(), sB.w(), sC.w());
-  RCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   // The quotient stage is enqueued FIRST, on a stream of its own: its launches cost the host ~0.1 ms, an MSM submission 0.5-0.7 ms, and the quotient's MSM is the end of the
   // critical path (on a shard of a proof the chain used to start 2.4 ms into the proof, behind three submissions; on one GPU it delayed the collection of the proof before).
   // A, B and the first part of C only need (A w), (B w) and the wires: their input event is recorded on `s`, which the chain is not on.
@@ -610,16 +589,16 @@ static int prove_submit(zkt_groth16_pk* pk, int ps, const uint64_t* wires, bool 
   if (pk->qcnt) {                       // (an empty range of the quotient's bases — n = 1, or more ranks than bases — has nothing to evaluate)
     q = pk->sq;
     const size_t M = pk->M, Q = pk->Q, QM = Q * M;
-    RCHK(hipEventRecord(pk->e_head, s)); RCHK(hipStreamWaitEvent(q, pk->e_head, 0));
+    HIPCHK(hipEventRecord(pk->e_head, s)); HIPCHK(hipStreamWaitEvent(q, pk->e_head, 0));
     // a, b, c side by side (grid.y): 2 + 2 k launches for transforms of k passes instead of 3 (1 + 2 k)
-    hipLaunchKernelGGL(k_prep_blocks, dim3(nb(QM), 3), dim3(256), 0, q, (const uint32_t*)pk->z_m[0].w(), (const uint32_t*)pk->z_m[1].w(), (const uint32_t*)pk->z_m[2].w(),
+    hipLaunchKernelGGL(k_prep_blocks, dim3(grid_blocks(QM), 3), dim3(256), 0, q, (const uint32_t*)pk->z_m[0].w(), (const uint32_t*)pk->z_m[1].w(), (const uint32_t*)pk->z_m[2].w(),
                        (const uint32_t*)pk->cinv.w(), n, pk->Bi, Q, pk->X.w());
     ZCHK(ntt_forward(pk->X.w(), pk->logM, pk->tw.w(), pk->ghat.w(), q, Q, 3, QM));     // block spectrum * spectrum of its slice of 1/d (and 1/M)
-    if (Q > 1) hipLaunchKernelGGL(k_sum_blocks, dim3(nb(M), 3), dim3(256), 0, q, pk->X.w(), M, Q);
+    if (Q > 1) hipLaunchKernelGGL(k_sum_blocks, dim3(grid_blocks(M), 3), dim3(256), 0, q, pk->X.w(), M, Q);
     ZCHK(ntt_inverse(pk->X.w(), pk->logM, pk->twinv.w(), q, 1, 3, QM));
-    hipLaunchKernelGGL(k_hvals, dim3(nb(pk->qcnt)), dim3(256), 0, q, (const uint32_t*)pk->X.w(), QM, (const uint32_t*)pk->P.w(), pk->qs0, pk->qcnt, sC.w() + nC1 * FW);
-    RCHK(hipGetLastError());
-    RCHK(hipEventRecord(pk->e_q, q));
+    hipLaunchKernelGGL(k_hvals, dim3(grid_blocks(pk->qcnt)), dim3(256), 0, q, (const uint32_t*)pk->X.w(), QM, (const uint32_t*)pk->P.w(), pk->qs0, pk->qcnt, sC.w() + nC1 * FW);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(pk->e_q, q));
   }
   // the sums, longest first; the quotient part of C is the only one that waits for the NTT chain (its input event is recorded on `s` behind k_hvals)
   hipStream_t in = s;          // (waiting for the chain instead — all four sums behind it — was measured on a shard of 8: 8.2 ms against 7.6)
@@ -641,8 +620,8 @@ static int prove_collect(zkt_groth16_pk* pk, int ps, zkt_g1_affine* A, zkt_g2_af
   ZCHK(zkt_g1_msm_collect(pk->setC1, ps, nullptr, cp)); ZCHK(zkt_g1_msm_collect(pk->setC2, ps, nullptr, cp + ZKT_G1_PARTIAL_WORDS));
   if (dev_partials) {            // [A: ZKT_G1_PARTIAL_WORDS | B: ZKT_G2_PARTIAL_WORDS | C: ZKT_G1_PARTIAL_WORDS]
     ZCHK(zkt_g1_msm_collect(pk->setA, ps, nullptr, dev_partials)); ZCHK(zkt_g2_msm_collect(pk->setB, ps, nullptr, dev_partials + ZKT_G1_PARTIAL_WORDS));
-    RCHK(launch_msm_jac_add(G_G1, cp, cp + ZKT_G1_PARTIAL_WORDS, dev_partials + ZKT_G1_PARTIAL_WORDS + ZKT_G2_PARTIAL_WORDS, pk->s));
-    RCHK(hipStreamSynchronize(pk->s));
+    HIPCHK(launch_msm_jac_add(G_G1, cp, cp + ZKT_G1_PARTIAL_WORDS, dev_partials + ZKT_G1_PARTIAL_WORDS + ZKT_G2_PARTIAL_WORDS, pk->s));
+    HIPCHK(hipStreamSynchronize(pk->s));
     return ZKT_OK;
   }
   ZCHK(zkt_g1_msm_collect(pk->setA, ps, A, nullptr)); ZCHK(zkt_g2_msm_collect(pk->setB, ps, B, nullptr));

@@ -10,8 +10,6 @@
 
 namespace zkt {
 
-static inline unsigned nblk(size_t n, int tpb) { return (unsigned)((n + tpb - 1) / tpb); }
-
 template <class F>
 __global__ void __launch_bounds__(64) k_group_add(const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {   // out may alias a
   size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -41,11 +39,11 @@ __global__ void __launch_bounds__(64) k_group_mul(const uint32_t* __restrict__ p
 }
 
 template <class F> static hipError_t add_t(const uint32_t* a, const uint32_t* b, uint32_t* o, size_t n, hipStream_t s) {
-  hipLaunchKernelGGL(k_group_add<F>, dim3(nblk(n, 64)), dim3(64), 0, s, a, b, o, n); return hipGetLastError(); }
+  hipLaunchKernelGGL(k_group_add<F>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, a, b, o, n); return hipGetLastError(); }
 template <class F> static hipError_t neg_t(const uint32_t* a, uint32_t* o, size_t n, hipStream_t s) {
-  hipLaunchKernelGGL(k_group_neg<F>, dim3(nblk(n, 64)), dim3(64), 0, s, a, o, n); return hipGetLastError(); }
+  hipLaunchKernelGGL(k_group_neg<F>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, a, o, n); return hipGetLastError(); }
 template <class F> static hipError_t mul_t(const uint32_t* p, bool fixed, const uint32_t* k, int kw, bool fixed_k, uint32_t* o, size_t n, hipStream_t s) {
-  hipLaunchKernelGGL(k_group_mul<F>, dim3(nblk(n, 64)), dim3(64), 0, s, p, fixed ? 0 : PtIO<F>::WORDS, k, kw, fixed_k ? 0 : kw, o, n); return hipGetLastError(); }
+  hipLaunchKernelGGL(k_group_mul<F>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, p, fixed ? 0 : PtIO<F>::WORDS, k, kw, fixed_k ? 0 : kw, o, n); return hipGetLastError(); }
 
 hipError_t launch_group_add(int grp, const uint32_t* a, const uint32_t* b, uint32_t* o, size_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
@@ -85,7 +83,7 @@ __global__ void __launch_bounds__(64) k_group_pred(const uint32_t* __restrict__ 
 }
 hipError_t launch_group_pred(int grp, int pred, const uint32_t* pts, const uint32_t* order, int order_words, uint32_t* out, size_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  dim3 g(nblk(n, 64)), t(64);
+  dim3 g(grid_blocks(n, 64)), t(64);
 #define ZKT_PRED(F) if (pred == 0) hipLaunchKernelGGL((k_group_pred<F, 0>), g, t, 0, s, pts, order, order_words, out, n); \
                     else hipLaunchKernelGGL((k_group_pred<F, 1>), g, t, 0, s, pts, order, order_words, out, n)
   switch (grp) { case G_G1: ZKT_PRED(FqOps); break; case G_G2: ZKT_PRED(Fq2Ops); break; case G_SECP: ZKT_PRED(SpOps); break; default: return hipErrorInvalidValue; }
@@ -106,7 +104,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 hipError_t launch_g1_fits(const G1Fits& f, int K, uint32_t* out, size_t n, hipStream_t s) {
   if (n == 0 || K == 0) return hipSuccess;
   if (K < 0 || K > 4) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_g1_fits, dim3(nblk(n, 64), (unsigned)K), dim3(64), 0, s, f, out, n);
+  hipLaunchKernelGGL(k_g1_fits, dim3(grid_blocks(n, 64), (unsigned)K), dim3(64), 0, s, f, out, n);
   return hipGetLastError();
 }
 
@@ -129,9 +127,9 @@ hipError_t launch_group_mul_segs(int grp, const MulSegs& segs, int kw, hipStream
   for (int k = 0; k < segs.n; ++k) total += segs.s[k].count;
   if (total == 0) return hipSuccess;
   switch (grp) {
-    case G_G1: hipLaunchKernelGGL(k_group_mul_segs<FqOps>, dim3(nblk(total, 64)), dim3(64), 0, s, segs, kw, total); break;
-    case G_G2: hipLaunchKernelGGL(k_group_mul_segs<Fq2Ops>, dim3(nblk(total, 64)), dim3(64), 0, s, segs, kw, total); break;
-    case G_SECP: hipLaunchKernelGGL(k_group_mul_segs<SpOps>, dim3(nblk(total, 64)), dim3(64), 0, s, segs, kw, total); break;
+    case G_G1: hipLaunchKernelGGL(k_group_mul_segs<FqOps>, dim3(grid_blocks(total, 64)), dim3(64), 0, s, segs, kw, total); break;
+    case G_G2: hipLaunchKernelGGL(k_group_mul_segs<Fq2Ops>, dim3(grid_blocks(total, 64)), dim3(64), 0, s, segs, kw, total); break;
+    case G_SECP: hipLaunchKernelGGL(k_group_mul_segs<SpOps>, dim3(grid_blocks(total, 64)), dim3(64), 0, s, segs, kw, total); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -212,8 +210,8 @@ hipError_t launch_generator_mul(int grp, const uint32_t* gen_abi, const uint32_t
       T.dev = mem;
     }
   }
-  if (grp == G_G1) hipLaunchKernelGGL(k_generator_mul<FqOps>, dim3(nblk(n, 64)), dim3(64), 0, s, (const uint32_t*)T.dev, k, out, n);
-  else hipLaunchKernelGGL(k_generator_mul<Fq2Ops>, dim3(nblk(n, 64)), dim3(64), 0, s, (const uint32_t*)T.dev, k, out, n);
+  if (grp == G_G1) hipLaunchKernelGGL(k_generator_mul<FqOps>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, (const uint32_t*)T.dev, k, out, n);
+  else hipLaunchKernelGGL(k_generator_mul<Fq2Ops>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, (const uint32_t*)T.dev, k, out, n);
   return hipGetLastError();
 }
 
@@ -326,7 +324,7 @@ hipError_t launch_stmt_wide_tables(const uint32_t* tab16, int n_pts, uint32_t* t
 }
 hipError_t launch_stmt_sums_wide(const uint32_t* tables, const uint32_t* stmt, int n_stmt, uint32_t* out, size_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_stmt_sums_wide, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, tables, stmt, n_stmt, out, n);
+  hipLaunchKernelGGL(k_stmt_sums_wide, dim3(grid_blocks(n, 64)), dim3(64), 0, s, tables, stmt, n_stmt, out, n);
   return hipGetLastError();
 }
 hipError_t launch_fixed_muls(int grp, const FixedMuls& f, hipStream_t s) {
@@ -400,7 +398,7 @@ __global__ void __launch_bounds__(64) k_group_sum_finish(const uint32_t* __restr
   if (threadIdx.x == 0) PtIO<F>::st(out, jac_to_aff(acc));
 }
 template <class F> static hipError_t sum_t(uint32_t* pts, size_t n, uint32_t* scratch, hipStream_t s) {
-  const int nb = (int)(n < (size_t)SUM_BLOCKS * 64 ? (n + 63) / 64 : SUM_BLOCKS);
+  const int nb = (int)(n < (size_t)SUM_BLOCKS * 64 ? grid_blocks(n, 64) : SUM_BLOCKS);
   hipLaunchKernelGGL(k_group_sum_partials<F>, dim3(nb), dim3(64), 0, s, (const uint32_t*)pts, n, scratch);
   hipLaunchKernelGGL(k_group_sum_finish<F>, dim3(1), dim3(64), 0, s, (const uint32_t*)scratch, nb, pts);     // result in pts[0]
   return hipGetLastError();

@@ -15,6 +15,9 @@ enum GroupId { G_G1 = 0, G_G2 = 1, G_SECP = 2 };
 // error word: index of the first offending element, or ~0ull
 static constexpr unsigned long long NO_ERR = ~0ull;
 
+// blocks of tpb threads that cover n work items (host code: launch grids)
+static inline unsigned grid_blocks(size_t n, unsigned tpb = 256) { return (unsigned)((n + tpb - 1) / tpb); }
+
 hipError_t launch_fp_op(int field, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n,
                         unsigned long long* err, hipStream_t s);
 // pow (prime_field_elem.rs:311-328): out[i] = a[i]^e_i, exponents of e_words u32 words each (shared: one exponent for all elements)
@@ -151,3 +154,16 @@ hipError_t launch_msm_jac_sum_to_affine(int grp, const uint32_t* jac_partials, s
 // G2 bucket accumulation with two lanes per task (zkt_msm_g2pair.hip, a translation unit with its own namespace): global scope
 hipError_t zkt_launch_accumulate_g2_pair(const uint32_t* table, const uint32_t* entries, const uint32_t* offsets, const void* order, const uint32_t* task_off,
                                          size_t nbuckets, uint32_t* sums, uint32_t* partial, size_t max_tasks, hipStream_t s);
+
+// ---- hooks between the C ABI translation units (global scope; the linkage of each is that of its definition) ------------------------------
+// zkt_api.cpp
+int zkt_internal_ready();                           // the library is initialised; sets the calling thread's device to the library's
+hipStream_t zkt_internal_stream();                  // the library's staging stream
+void zkt_internal_set_error_index(size_t i);        // what zkt_last_error_index reports on this thread
+// `dst` works on `src`'s streams from now on (zkt_api.cpp has the details)
+extern "C" int zkt_internal_bases_share_streams(void* dst, void* src, int share_acc, int tail_base, int tail_span);
+// combine step of a sharded MSM: `count` Jacobian partials, `stride_words` u32 apart, summed and normalised to one affine ABI point at host `out`
+extern "C" int zkt_internal_jac_sum(int grp, const uint32_t* dev_partials, size_t count, size_t stride_words, hipStream_t s, void* out);
+// zkt_shutdown: device memory held by the per-key caches of zkt_protocols.hip and zkt_pinocchio.hip
+extern "C" void zkt_internal_clear_caches();
+extern "C" void zkt_pinocchio_clear_caches();

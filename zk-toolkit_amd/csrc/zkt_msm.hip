@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(64) k_to_kernel_layout(const uint32_t* __restr
 #endif
 hipError_t PART(launch_msm_to_kernel_layout)(int grp, const uint32_t* abi, uint32_t* mont, uint8_t* inf, size_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  MSM_DISPATCH(grp, hipLaunchKernelGGL(k_to_kernel_layout<F>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, abi, mont, inf, n));
+  MSM_DISPATCH(grp, hipLaunchKernelGGL(k_to_kernel_layout<F>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, abi, mont, inf, n));
   return hipGetLastError();
 }
 
@@ -707,7 +707,7 @@ static hipError_t zero_async(void* ptr, size_t bytes, hipStream_t s) {
   const size_t quads = words / 4; const int tail = (int)(words % 4);
   size_t items = quads > (size_t)tail ? quads : (size_t)tail;
   if (items < (size_t)head) items = (size_t)head;
-  hipLaunchKernelGGL(k_zero_words, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (uint32_t*)ptr, head, quads, tail);
+  hipLaunchKernelGGL(k_zero_words, dim3(grid_blocks(items)), dim3(256), 0, s, (uint32_t*)ptr, head, quads, tail);
   return hipGetLastError();
 }
 // stage 1 (atomic/memory bound): signed digits, counting sort by bucket, bucket order by population
@@ -731,7 +731,7 @@ hipError_t PART(launch_msm_sort)(const MsmPlan& P, const uint8_t* inf, const uin
     hipLaunchKernelGGL(k_part_chunks<true>, dim3(pd.maxblk), dim3(256), 0, s, (const uint32_t*)w.tileoff, pd.P, pd.ntiles, (const uint32_t*)w.blkoff, (const uint2*)w.rec,
                        w.subhist, (const uint32_t*)w.offsets, B, w.entries);
   } else if (n) {
-    const unsigned g = (unsigned)((n + 255) / 256);
+    const unsigned g = grid_blocks(n);
     const uint32_t wb = P.direct ? (uint32_t)P.half : 0u;
     hipLaunchKernelGGL(k_digits<false>, dim3(g), dim3(256), 0, s, scalars, inf, n, P.c, P.nwin, wb, w.counts, (const uint32_t*)nullptr, w.slot, (uint32_t*)nullptr);
     launch_scan(w.counts, w.offsets, B, w.scan_tmp, s);
@@ -739,9 +739,9 @@ hipError_t PART(launch_msm_sort)(const MsmPlan& P, const uint8_t* inf, const uin
   } else {
     if ((e = zero_async(w.offsets, (B + 1) * 4, s)) != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(k_task_count, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, w.counts, B, P.chunk, w.ntask, w.size_hist);
+  hipLaunchKernelGGL(k_task_count, dim3(grid_blocks(B)), dim3(256), 0, s, w.counts, B, P.chunk, w.ntask, w.size_hist);
   launch_scan(w.ntask, w.task_off, B, w.scan_tmp, s);
-  hipLaunchKernelGGL(k_task_scatter, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, w.counts, B, P.chunk, (const uint32_t*)w.size_hist, w.size_cur, w.order, w.hot);
+  hipLaunchKernelGGL(k_task_scatter, dim3(grid_blocks(B)), dim3(256), 0, s, w.counts, B, P.chunk, (const uint32_t*)w.size_hist, w.size_cur, w.order, w.hot);
   return hipGetLastError();
 }
 // stage 2 (VALU bound, the dominant kernel): one bucket per lane
@@ -752,7 +752,7 @@ hipError_t PART(launch_msm_accumulate)(const MsmPlan& P, const uint32_t* table, 
     return ::zkt_launch_accumulate_g2_pair(table, (const uint32_t*)w.entries, (const uint32_t*)w.offsets, (const void*)w.order, (const uint32_t*)w.task_off, P.nbuckets,
                                            w.sums, w.partial, w.max_tasks, s);
 #endif
-  MSM_DISPATCH(P.grp, hipLaunchKernelGGL(k_accumulate<F>, dim3((unsigned)((w.max_tasks + 63) / 64)), dim3(64), 0, s, table, (const uint32_t*)w.entries,
+  MSM_DISPATCH(P.grp, hipLaunchKernelGGL(k_accumulate<F>, dim3(grid_blocks(w.max_tasks, 64)), dim3(64), 0, s, table, (const uint32_t*)w.entries,
                                          (const uint32_t*)w.offsets, (const uint2*)w.order, (const uint32_t*)w.task_off, P.nbuckets, w.sums, w.partial));
   return hipGetLastError();
 }
@@ -792,7 +792,7 @@ hipError_t PART(launch_msm_reduce)(const MsmPlan& P, void* workspace, uint32_t* 
 // window-multiple table build
 hipError_t PART(launch_msm_precompute)(int grp, uint32_t* table, uint8_t* inf, size_t n, int c, int nwin, uint32_t* tmp, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  MSM_DISPATCH(grp, hipLaunchKernelGGL(k_precompute<F>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, table, inf, n, c, nwin, tmp));
+  MSM_DISPATCH(grp, hipLaunchKernelGGL(k_precompute<F>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, table, inf, n, c, nwin, tmp));
   return hipGetLastError();
 }
 

@@ -86,7 +86,7 @@ k_accumulate_g2_pair(const uint32_t* __restrict__ table, const uint32_t* __restr
 hipError_t zkt_launch_accumulate_g2_pair(const uint32_t* table, const uint32_t* entries, const uint32_t* offsets, const void* order, const uint32_t* task_off,
                                          size_t nbuckets, uint32_t* sums, uint32_t* partial, size_t max_tasks, hipStream_t s) {
   if (max_tasks == 0) return hipSuccess;
-  hipLaunchKernelGGL(zkt_g2pair::k_accumulate_g2_pair, dim3((unsigned)((2 * max_tasks + 63) / 64)), dim3(64), 0, s, table, entries, offsets, (const uint2*)order, task_off,
+  hipLaunchKernelGGL(zkt_g2pair::k_accumulate_g2_pair, dim3(zkt_g2pair::grid_blocks(2 * max_tasks, 64)), dim3(64), 0, s, table, entries, offsets, (const uint2*)order, task_off,
                      nbuckets, sums, partial);
   return hipGetLastError();
 }

@@ -25,7 +25,7 @@ __global__ void __launch_bounds__(64) k_miller_exact(int which, const uint32_t* 
 }
 hipError_t launch_miller_exact(int which, const uint32_t* g1, const uint32_t* g2, uint32_t* out, size_t n, unsigned long long* err, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_miller_exact, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, which, g1, g2, out, n, err);
+  hipLaunchKernelGGL(k_miller_exact, dim3(grid_blocks(n, 64)), dim3(64), 0, s, which, g1, g2, out, n, err);
   return hipGetLastError();
 }
 
@@ -65,12 +65,12 @@ __global__ void __launch_bounds__(64) k_ate_guards(PairArgs a, int K, uint32_t* 
 }
 hipError_t launch_ate_guards(const PairArgs& a, int K, uint32_t* flags, size_t n, hipStream_t s, uint32_t p_skip) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_ate_guards, dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, s, a, K, flags, n, p_skip);
+  hipLaunchKernelGGL(k_ate_guards, dim3(grid_blocks(4 * n, 64)), dim3(64), 0, s, a, K, flags, n, p_skip);
   return hipGetLastError();
 }
 hipError_t launch_short_loop_guards(const PairArgs& a, int K, uint32_t* flags, size_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_short_loop_guards, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, a, K, flags, n);
+  hipLaunchKernelGGL(k_short_loop_guards, dim3(grid_blocks(n, 64)), dim3(64), 0, s, a, K, flags, n);
   return hipGetLastError();
 }
 namespace {
@@ -337,7 +337,7 @@ int verify_fail_closed() { return g_fail_closed.load(); }
 // entry points block on their result anyway); honest batches stop there.  fail-closed mode: the marks become rejections, no read-back.
 static hipError_t finish_exact(const PairArgs& a, int K, const uint8_t* kcount, const uint32_t* target, uint32_t* ok, size_t n, unsigned long long* err, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  const dim3 g256((unsigned)((n + 255) / 256));
+  const dim3 g256(grid_blocks(n));
   if (verify_fail_closed()) { hipLaunchKernelGGL(k_count_exact, g256, dim3(256), 0, s, (const uint32_t*)ok, n, (uint32_t*)nullptr, 1); return hipGetLastError(); }
   uint32_t* d = nullptr; uint32_t host = 0; hipError_t e;
   if ((e = hipMallocAsync((void**)&d, 4, s)) != hipSuccess) return e;
@@ -346,7 +346,7 @@ static hipError_t finish_exact(const PairArgs& a, int K, const uint8_t* kcount, 
   if ((e = hipMemcpyAsync(&host, d, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) { (void)hipFreeAsync(d, s); return e; }
   if ((e = hipFreeAsync(d, s)) != hipSuccess) return e;
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-  if (host) hipLaunchKernelGGL(k_product_exact_marked, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, a, K, kcount, target, ok, n, err);
+  if (host) hipLaunchKernelGGL(k_product_exact_marked, dim3(grid_blocks(n, 64)), dim3(64), 0, s, a, K, kcount, target, ok, n, err);
   return hipGetLastError();
 }
 static PairArgs groth16_pairs(const uint32_t* A, const uint32_t* B, const uint32_t* C, const uint32_t* S, const uint32_t* gamma, const uint32_t* delta) {
@@ -371,7 +371,7 @@ hipError_t launch_groth16_verify_small(const uint32_t* A, const uint32_t* B, con
     e = launch_group_mul_segs(G_G1, segs, 8, s);
   }
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_stmt_sums, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const uint32_t*)tmp, n_stmt, S, n);
+  hipLaunchKernelGGL(k_stmt_sums, dim3(grid_blocks(n, 64)), dim3(64), 0, s, (const uint32_t*)tmp, n_stmt, S, n);
   PairArgs a{};
   a.g1[0] = A; a.s1[0] = ABI_G1_WORDS; a.g2[0] = B; a.s2[0] = ABI_G2_WORDS; a.neg[0] = 0;
   a.g1[1] = S; a.s1[1] = ABI_G1_WORDS; a.g2[1] = gamma; a.s2[1] = 0; a.neg[1] = 1;
@@ -384,9 +384,9 @@ hipError_t launch_groth16_verify_small(const uint32_t* A, const uint32_t* B, con
   if ((e = guard_fork(s, &side)) != hipSuccess || (e = (ate ? launch_ate_guards(a, 3, flags, n, side, 2u) : launch_short_loop_guards(a, 3, flags, n, side))) != hipSuccess ||
       (e = (ate ? launch_dproduct_ate(a, 3, ate_target, ok, n, err, s) : launch_dproduct(a, 3, alpha_beta, ok, n, err, s))) != hipSuccess ||
       (e = guard_join(s, side)) != hipSuccess) { (void)hipFreeAsync(flags, s); return e; }
-  hipLaunchKernelGGL(k_product_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint32_t*)flags, ok, n);
+  hipLaunchKernelGGL(k_product_resolve, dim3(grid_blocks(n)), dim3(256), 0, s, (const uint32_t*)flags, ok, n);
   if ((e = hipFreeAsync(flags, s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_groth16_verify<false>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, A, B, C, uvw_stmt, stmt, n_stmt, gamma, delta, alpha_beta, ok, n, err, 1, (const uint32_t*)nullptr, (const uint32_t*)S);
+  hipLaunchKernelGGL(k_groth16_verify<false>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, A, B, C, uvw_stmt, stmt, n_stmt, gamma, delta, alpha_beta, ok, n, err, 1, (const uint32_t*)nullptr, (const uint32_t*)S);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   return finish_exact(a, 3, nullptr, alpha_beta, ok, n, err, s);
 }
@@ -403,9 +403,9 @@ hipError_t launch_groth16_verify(const uint32_t* A, const uint32_t* B, const uin
     if ((e = hipMallocAsync((void**)&fits, 2 * n * sizeof(uint32_t), s)) != hipSuccess) { (void)hipFreeAsync(S, s); return e; }
     G1Fits gf{}; gf.pts[0] = A; gf.stride[0] = ABI_G1_WORDS; gf.pts[1] = C; gf.stride[1] = ABI_G1_WORDS;
     if ((e = launch_g1_fits(gf, 2, fits, n, s)) != hipSuccess) { (void)hipFreeAsync(S, s); (void)hipFreeAsync(fits, s); return e; }
-    hipLaunchKernelGGL(k_groth16_verify_ate, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, A, B, C, (const uint32_t*)S, ate_key, ok, n, err, (const uint32_t*)fits);
+    hipLaunchKernelGGL(k_groth16_verify_ate, dim3(grid_blocks(n, 64)), dim3(64), 0, s, A, B, C, (const uint32_t*)S, ate_key, ok, n, err, (const uint32_t*)fits);
     if ((e = hipFreeAsync(fits, s)) != hipSuccess) { (void)hipFreeAsync(S, s); return e; }
-    hipLaunchKernelGGL(k_groth16_verify<false>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, A, B, C, uvw_stmt, stmt, n_stmt, gamma, delta, alpha_beta, ok, n, err, 1, (const uint32_t*)nullptr, (const uint32_t*)S);
+    hipLaunchKernelGGL(k_groth16_verify<false>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, A, B, C, uvw_stmt, stmt, n_stmt, gamma, delta, alpha_beta, ok, n, err, 1, (const uint32_t*)nullptr, (const uint32_t*)S);
     if ((e = hipGetLastError()) != hipSuccess || (e = finish_exact(groth16_pairs(A, B, C, S, gamma, delta), 3, nullptr, alpha_beta, ok, n, err, s)) != hipSuccess) { (void)hipFreeAsync(S, s); return e; }
     if ((e = hipFreeAsync(S, s)) != hipSuccess) return e;
     return hipGetLastError();
@@ -422,13 +422,13 @@ hipError_t launch_groth16_verify(const uint32_t* A, const uint32_t* B, const uin
     MulSegs segs; segs.n = n_stmt;
     for (int j = 0; j < n_stmt; ++j) segs.s[j] = MulSeg{uvw_stmt + (size_t)j * ABI_G1_WORDS, stmt + (size_t)j * 8, tmp + (size_t)j * n * ABI_G1_WORDS, (uint32_t)n, 0u, (uint32_t)(n_stmt * 8)};
     if ((e = launch_group_mul_segs(G_G1, segs, 8, s)) != hipSuccess) { (void)hipFreeAsync(good, s); (void)hipFreeAsync(tmp, s); (void)hipFreeAsync(S, s); return e; }
-    hipLaunchKernelGGL(k_stmt_sums, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const uint32_t*)tmp, n_stmt, S, n);
+    hipLaunchKernelGGL(k_stmt_sums, dim3(grid_blocks(n, 64)), dim3(64), 0, s, (const uint32_t*)tmp, n_stmt, S, n);
   }
-  hipLaunchKernelGGL(k_groth16_verify<true>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, A, B, C, uvw_stmt, stmt, n_stmt, gamma, delta, alpha_beta, ok, n, err, 0, (const uint32_t*)good, (const uint32_t*)S);
-  hipLaunchKernelGGL(k_groth16_verify<false>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, A, B, C, uvw_stmt, stmt, n_stmt, gamma, delta, alpha_beta, ok, n, err, 1, (const uint32_t*)nullptr, (const uint32_t*)S);
+  hipLaunchKernelGGL(k_groth16_verify<true>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, A, B, C, uvw_stmt, stmt, n_stmt, gamma, delta, alpha_beta, ok, n, err, 0, (const uint32_t*)good, (const uint32_t*)S);
+  hipLaunchKernelGGL(k_groth16_verify<false>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, A, B, C, uvw_stmt, stmt, n_stmt, gamma, delta, alpha_beta, ok, n, err, 1, (const uint32_t*)nullptr, (const uint32_t*)S);
   if (!S) {                                  // statements the batched multiplication does not take (n_stmt = 0 or > 12): the sums of the marked elements, one lane each
     if ((e = hipMallocAsync((void**)&S, n * ABI_G1_WORDS * 4, s)) != hipSuccess) { (void)hipFreeAsync(good, s); return e; }
-    hipLaunchKernelGGL(k_stmt_sums_marked, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, uvw_stmt, stmt, n_stmt, (const uint32_t*)ok, S, n);
+    hipLaunchKernelGGL(k_stmt_sums_marked, dim3(grid_blocks(n, 64)), dim3(64), 0, s, uvw_stmt, stmt, n_stmt, (const uint32_t*)ok, S, n);
   }
   if ((e = hipGetLastError()) != hipSuccess || (e = finish_exact(groth16_pairs(A, B, C, S, gamma, delta), 3, nullptr, alpha_beta, ok, n, err, s)) != hipSuccess) {
     (void)hipFreeAsync(good, s); if (tmp) (void)hipFreeAsync(tmp, s); (void)hipFreeAsync(S, s); return e; }
@@ -475,13 +475,13 @@ hipError_t launch_pairing_product_check_counts(const PairArgs& a, int K, const u
   if ((e = guard_fork(s, &side)) != hipSuccess || (e = launch_ate_guards(a, K, flags, n, side)) != hipSuccess ||          // the unused slots repeat pair 0: same verdict
       (e = launch_dproduct_ate(a, K, nullptr, ok, n, err, s, kcount)) != hipSuccess ||
       (e = guard_join(s, side)) != hipSuccess) { (void)hipFreeAsync(flags, s); return e; }
-  hipLaunchKernelGGL(k_product_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint32_t*)flags, ok, n);
+  hipLaunchKernelGGL(k_product_resolve, dim3(grid_blocks(n)), dim3(256), 0, s, (const uint32_t*)flags, ok, n);
   if ((e = hipFreeAsync(flags, s)) != hipSuccess) return e;
   return hipGetLastError();
 }
 hipError_t launch_pairing_product_check(const PairArgs& a, int K, uint32_t* ok, size_t n, unsigned long long* err, hipStream_t s, uint32_t p_trusted) {
   if (n == 0) return hipSuccess;
-  dim3 g((unsigned)((n + 63) / 64)), t(64);
+  dim3 g(grid_blocks(n, 64)), t(64);
   const bool small = n * (size_t)K <= dproduct_limit();
   if (K < 1 || K > 4) return hipErrorInvalidValue;
   if (small) {                             // the 63-step loop on the lane-distributed kernels, its preconditions checked beside it
@@ -489,7 +489,7 @@ hipError_t launch_pairing_product_check(const PairArgs& a, int K, uint32_t* ok, 
     if ((e = hipMallocAsync((void**)&flags, n * sizeof(uint32_t), s)) != hipSuccess) return e;
     if ((e = guard_fork(s, &side)) != hipSuccess || (e = launch_ate_guards(a, K, flags, n, side, p_trusted)) != hipSuccess ||
         (e = launch_dproduct_ate(a, K, nullptr, ok, n, err, s)) != hipSuccess || (e = guard_join(s, side)) != hipSuccess) { (void)hipFreeAsync(flags, s); return e; }
-    hipLaunchKernelGGL(k_product_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint32_t*)flags, ok, n);
+    hipLaunchKernelGGL(k_product_resolve, dim3(grid_blocks(n)), dim3(256), 0, s, (const uint32_t*)flags, ok, n);
     if ((e = hipFreeAsync(flags, s)) != hipSuccess) return e;
   }
   // large batches: the 63-step loop decides; what it marks (an argument outside its group) goes to the 255-step kernel as before

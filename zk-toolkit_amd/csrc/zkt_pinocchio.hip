@@ -13,6 +13,7 @@
 #include "abi.h"
 #include "zkt_internal.h"
 #include "../../include/zkt.h"
+#include "host_abi.h"
 
 namespace zkt {
 typedef FrC C;
@@ -73,28 +74,6 @@ __global__ void __launch_bounds__(64) k_pin_sums(PinSums p) {
 }  // namespace zkt
 
 using namespace zkt;
-
-namespace {
-struct Dev {
-  void* p = nullptr;
-  explicit Dev(size_t bytes) { if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) p = nullptr; }
-  ~Dev() { if (p) hipFree(p); }
-  uint32_t* w() const { return (uint32_t*)p; }
-  Dev(const Dev&) = delete; Dev& operator=(const Dev&) = delete;
-};
-#define QCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[zkt] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return ZKT_ERR_DEVICE; } } while (0)
-#define ZRC(x) do { int _rc = (x); if (_rc != ZKT_OK) return _rc; } while (0)
-const size_t G1B = sizeof(zkt_g1_affine), G2B = sizeof(zkt_g2_affine), FRB = 32;
-const uint64_t G1_GEN[13] = {0xfb3af00adb22c6bbull, 0x6c55e83ff97a1aefull, 0xa14e3a3f171bac58ull, 0xc3688c4f9774b905ull, 0x2695638c4fa9ac0full, 0x17f1d3a73197d794ull,
-                             0x0caa232946c5e7e1ull, 0xd03cc744a2888ae4ull, 0x00db18cb2c04b3edull, 0xfcf5e095d5d00af6ull, 0xa09e30ed741d8ae4ull, 0x08b3f481e3aaa0f1ull, 0};   // g1_point.rs:38-47
-const uint64_t G2_GEN[25] = {0xe5ac7d055d042b7eull, 0x334cf11213945d57ull, 0xb5da61bbdc7f5049ull, 0x596bd0d09920b61aull, 0x7dacd3a088274f65ull, 0x13e02b6052719f60ull,
-                             0xd48056c8c121bdb8ull, 0x0bac0326a805bbefull, 0xb4510b647ae3d177ull, 0xc6e47ad4fa403b02ull, 0x260805272dc51051ull, 0x024aa2b2f08f0a91ull,
-                             0xaaa9075ff05f79beull, 0x3f370d275cec1da1ull, 0x267492ab572e99abull, 0xcb3e287e85a763afull, 0x32acd2b02bc28b99ull, 0x0606c4a02ea734ccull,
-                             0xe193548608b82801ull, 0x923ac9cc3baca289ull, 0x6d429a695160d12cull, 0xadfd9baa8cbdd3a7ull, 0x8cc9cdc6da2e351aull, 0x0ce5d527727d6e11ull, 0};   // g2_point.rs:36-46
-}  // namespace
-
-extern int zkt_internal_ready();   // zkt_api.cpp
-extern void zkt_internal_set_error_index(size_t i);
 
 // ---- verification with the key's io points as fixed-base tables ------------------------------------------------------------------
 // A verifier checks many proofs against ONE key.  The statement sums sum_i io_i * {vk_io, yk_io, wk_io}[i] (verifier.rs:70-76) through the one-shot
@@ -234,34 +213,32 @@ int zkt_pinocchio_setup(zkt_pinocchio_crs* c, const uint64_t* vi, const uint64_t
   Dev dP(rows * n * FRB), drnd(256), dve(rows * FRB), dwe(rows * FRB), dye(rows * FRB), dcols(7 * rows * FRB), dsing(10 * FRB), dpow(deg * FRB);
   Dev dgen1(G1B), dgen2(G2B), d1(7 * rows * G1B), d2((rows + deg) * G2B), ds1(10 * G1B), ds2(10 * G2B);
   if (!dP.p || !dcols.p || !d1.p || !d2.p || !ds1.p || !ds2.p || !dpow.p) return ZKT_ERR_DEVICE;
-  QCHK(hipMemcpyAsync(drnd.p, rnd, 256, hipMemcpyHostToDevice, s));
-  QCHK(hipMemcpyAsync(dgen1.p, G1_GEN, G1B, hipMemcpyHostToDevice, s)); QCHK(hipMemcpyAsync(dgen2.p, G2_GEN, G2B, hipMemcpyHostToDevice, s));
+  ZCHK(up(drnd, rnd, 256, s)); ZCHK(up(dgen1, &G1_GEN, G1B, s)); ZCHK(up(dgen2, &G2_GEN, G2B, s));
   const uint64_t* polys[3] = {vi, wi, yi}; Dev* ev[3] = {&dve, &dwe, &dye};
   for (int k = 0; k < 3; ++k) {
-    QCHK(hipMemcpyAsync(dP.p, polys[k], rows * n * FRB, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_pin_poly_eval, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, (const uint32_t*)dP.w(), rows, n, (const uint32_t*)(drnd.w() + 56), ev[k]->w());
+    ZCHK(up(dP, polys[k], rows * n * FRB, s));
+    hipLaunchKernelGGL(k_pin_poly_eval, dim3(grid_blocks(rows, 64)), dim3(64), 0, s, (const uint32_t*)dP.w(), rows, n, (const uint32_t*)(drnd.w() + 56), ev[k]->w());
   }
-  hipLaunchKernelGGL(k_pin_scalars, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, (const uint32_t*)dve.w(), (const uint32_t*)dwe.w(), (const uint32_t*)dye.w(),
+  hipLaunchKernelGGL(k_pin_scalars, dim3(grid_blocks(rows, 64)), dim3(64), 0, s, (const uint32_t*)dve.w(), (const uint32_t*)dwe.w(), (const uint32_t*)dye.w(),
                      (const uint32_t*)drnd.w(), n, rows, dcols.w(), dsing.w());
-  hipLaunchKernelGGL(k_pin_powseq, dim3((unsigned)((deg + 255) / 256)), dim3(256), 0, s, (const uint32_t*)(drnd.w() + 56), deg, dpow.w());
-  QCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_pin_powseq, dim3(grid_blocks(deg)), dim3(256), 0, s, (const uint32_t*)(drnd.w() + 56), deg, dpow.w());
+  HIPCHK(hipGetLastError());
   // generator * scalar for every element
-  QCHK(launch_generator_mul(G_G1, dgen1.w(), dcols.w(), d1.w(), 7 * rows, s));
-  QCHK(launch_generator_mul(G_G2, dgen2.w(), dcols.w() + rows * 8, d2.w(), rows, s));                 // g2_w * w_i(s)
-  QCHK(launch_generator_mul(G_G2, dgen2.w(), dpow.w(), d2.w() + rows * 50, deg, s));                   // si
-  QCHK(launch_generator_mul(G_G1, dgen1.w(), dsing.w(), ds1.w(), 10, s));
-  QCHK(launch_generator_mul(G_G2, dgen2.w(), dsing.w(), ds2.w(), 10, s));
+  HIPCHK(launch_generator_mul(G_G1, dgen1.w(), dcols.w(), d1.w(), 7 * rows, s));
+  HIPCHK(launch_generator_mul(G_G2, dgen2.w(), dcols.w() + rows * 8, d2.w(), rows, s));                 // g2_w * w_i(s)
+  HIPCHK(launch_generator_mul(G_G2, dgen2.w(), dpow.w(), d2.w() + rows * 50, deg, s));                   // si
+  HIPCHK(launch_generator_mul(G_G1, dgen1.w(), dsing.w(), ds1.w(), 10, s));
+  HIPCHK(launch_generator_mul(G_G2, dgen2.w(), dsing.w(), ds2.w(), 10, s));
   auto g1col = [&](int col, size_t from) { return d1.w() + ((size_t)col * rows + from) * 26; };
-  auto dl = [&](void* h, const void* d, size_t bytes) -> int { if (bytes) QCHK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s)); return ZKT_OK; };
   zkt_g1_affine* mid1[7] = {c->vk_mid, c->g1_wk_mid, c->yk_mid, c->alpha_vk_mid, c->alpha_wk_mid, c->alpha_yk_mid, c->beta_vwy_k_mid};
-  for (int col = 0; col < 7; ++col) ZRC(dl(mid1[col], g1col(col, nio), nmid * G1B));
-  ZRC(dl(c->g2_wk_mid, d2.w() + nio * 50, nmid * G2B)); ZRC(dl(c->si, d2.w() + rows * 50, deg * G2B));
-  ZRC(dl(c->vk_io, g1col(0, 0), nio * G1B)); ZRC(dl(c->yk_io, g1col(2, 0), nio * G1B)); ZRC(dl(c->wk_io, d2.w(), nio * G2B));
+  for (int col = 0; col < 7; ++col) ZCHK(down(mid1[col], g1col(col, nio), nmid * G1B, s));
+  ZCHK(down(c->g2_wk_mid, d2.w() + nio * 50, nmid * G2B, s)); ZCHK(down(c->si, d2.w() + rows * 50, deg * G2B, s));
+  ZCHK(down(c->vk_io, g1col(0, 0), nio * G1B, s)); ZCHK(down(c->yk_io, g1col(2, 0), nio * G1B, s)); ZCHK(down(c->wk_io, d2.w(), nio * G2B, s));
   // singles: 0 one, 1 alpha_v, 2 alpha_w, 3 alpha_y, 4 gamma, 5 gamma beta, 6 T, 7 T alpha_v, 8 T alpha_y, 9 T beta
-  ZRC(dl(c->one_g1, ds1.w(), G1B)); ZRC(dl(c->one_g2, ds2.w(), G2B)); ZRC(dl(c->alpha_v, ds2.w() + 1 * 50, G2B)); ZRC(dl(c->alpha_w, ds1.w() + 2 * 26, G1B));
-  ZRC(dl(c->alpha_y, ds2.w() + 3 * 50, G2B)); ZRC(dl(c->gamma, ds2.w() + 4 * 50, G2B)); ZRC(dl(c->beta_gamma, ds2.w() + 5 * 50, G2B));
-  ZRC(dl(c->t, ds1.w() + 6 * 26, G1B)); ZRC(dl(c->alpha_v_t, ds1.w() + 7 * 26, G1B)); ZRC(dl(c->alpha_y_t, ds1.w() + 8 * 26, G1B)); ZRC(dl(c->beta_t, ds1.w() + 9 * 26, G1B));
-  QCHK(hipStreamSynchronize(s));
+  ZCHK(down(c->one_g1, ds1.w(), G1B, s)); ZCHK(down(c->one_g2, ds2.w(), G2B, s)); ZCHK(down(c->alpha_v, ds2.w() + 1 * 50, G2B, s)); ZCHK(down(c->alpha_w, ds1.w() + 2 * 26, G1B, s));
+  ZCHK(down(c->alpha_y, ds2.w() + 3 * 50, G2B, s)); ZCHK(down(c->gamma, ds2.w() + 4 * 50, G2B, s)); ZCHK(down(c->beta_gamma, ds2.w() + 5 * 50, G2B, s));
+  ZCHK(down(c->t, ds1.w() + 6 * 26, G1B, s)); ZCHK(down(c->alpha_v_t, ds1.w() + 7 * 26, G1B, s)); ZCHK(down(c->alpha_y_t, ds1.w() + 8 * 26, G1B, s)); ZCHK(down(c->beta_t, ds1.w() + 9 * 26, G1B, s));
+  HIPCHK(hipStreamSynchronize(s));
   return ZKT_OK;
 }
 
@@ -276,28 +253,28 @@ int zkt_pinocchio_prove(const zkt_pinocchio_crs* c, const uint64_t* wires, const
   zkt_g1_affine sv, sw1, sy, sav, saw, say, sb; zkt_g2_affine sw2;
   const zkt_g1_affine* bases1[7] = {c->vk_mid, c->g1_wk_mid, c->yk_mid, c->alpha_vk_mid, c->alpha_wk_mid, c->alpha_yk_mid, c->beta_vwy_k_mid};
   zkt_g1_affine* sums1[7] = {&sv, &sw1, &sy, &sav, &saw, &say, &sb};
-  for (int k = 0; k < 7; ++k) ZRC(zkt_g1_msm(bases1[k], wmid, nmid, sums1[k]));
-  ZRC(zkt_g2_msm(c->g2_wk_mid, wmid, nmid, &sw2));
+  for (int k = 0; k < 7; ++k) ZCHK(zkt_g1_msm(bases1[k], wmid, nmid, sums1[k]));
+  ZCHK(zkt_g2_msm(c->g2_wk_mid, wmid, nmid, &sw2));
   // randomisation terms (prover.rs:124-131): t dv, t dy, alpha_v_t dv, alpha_y_t dy, beta_t dv, beta_t dy
   zkt_g1_affine pts[6] = {*c->t, *c->t, *c->alpha_v_t, *c->alpha_y_t, *c->beta_t, *c->beta_t}, rnd[6];
   uint64_t sc[24];
   const uint64_t* which[6] = {delta_v, delta_y, delta_v, delta_y, delta_v, delta_y};
   for (int k = 0; k < 6; ++k) memcpy(sc + 4 * k, which[k], 32);
-  ZRC(zkt_g1_mul_batch(pts, sc, 4, rnd, 6));
+  ZCHK(zkt_g1_mul_batch(pts, sc, 4, rnd, 6));
   zkt_g1_affine bsum;
-  ZRC(zkt_g1_add_batch(&rnd[4], &rnd[5], &bsum, 1));
+  ZCHK(zkt_g1_add_batch(&rnd[4], &rnd[5], &bsum, 1));
   zkt_g1_affine lhs[4] = {rnd[0], rnd[1], rnd[2], rnd[3]}, rhs[4] = {sv, sy, sav, say}, out4[4];
-  ZRC(zkt_g1_add_batch(lhs, rhs, out4, 4));
+  ZCHK(zkt_g1_add_batch(lhs, rhs, out4, 4));
   *pf->v_mid_s = out4[0]; *pf->y_mid_s = out4[1]; *pf->alpha_v_mid_s = out4[2]; *pf->alpha_y_mid_s = out4[3];
-  ZRC(zkt_g1_add_batch(&bsum, &sb, pf->beta_vwy_mid_s, 1));
+  ZCHK(zkt_g1_add_batch(&bsum, &sb, pf->beta_vwy_mid_s, 1));
   *pf->g1_w_mid_s = sw1; *pf->g2_w_mid_s = sw2; *pf->alpha_w_mid_s = saw;
   // adjusted h(s) (prover.rs:148-161): h_s + w_s delta_v - one_g2 delta_y
   zkt_g2_affine h_s, w_io, w_s, wdv, ody, nody, t2;
-  ZRC(zkt_g2_msm(c->si, h, h_len, &h_s));
-  ZRC(zkt_g2_msm(c->wk_io, wires, nio, &w_io));
-  ZRC(zkt_g2_add_batch(&sw2, &w_io, &w_s, 1));
-  ZRC(zkt_g2_mul_batch(&w_s, delta_v, 4, &wdv, 1)); ZRC(zkt_g2_mul_batch(c->one_g2, delta_y, 4, &ody, 1)); ZRC(zkt_g2_neg_batch(&ody, &nody, 1));
-  ZRC(zkt_g2_add_batch(&h_s, &wdv, &t2, 1)); ZRC(zkt_g2_add_batch(&t2, &nody, pf->h_s, 1));
+  ZCHK(zkt_g2_msm(c->si, h, h_len, &h_s));
+  ZCHK(zkt_g2_msm(c->wk_io, wires, nio, &w_io));
+  ZCHK(zkt_g2_add_batch(&sw2, &w_io, &w_s, 1));
+  ZCHK(zkt_g2_mul_batch(&w_s, delta_v, 4, &wdv, 1)); ZCHK(zkt_g2_mul_batch(c->one_g2, delta_y, 4, &ody, 1)); ZCHK(zkt_g2_neg_batch(&ody, &nody, 1));
+  ZCHK(zkt_g2_add_batch(&h_s, &wdv, &t2, 1)); ZCHK(zkt_g2_add_batch(&t2, &nody, pf->h_s, 1));
   return ZKT_OK;
 }
 
@@ -308,7 +285,6 @@ int zkt_pinocchio_prove(const zkt_pinocchio_crs* c, const uint64_t* wires, const
 // upload the bases and build their plan on every call (50 ms at 32 constraints, seconds at 2^16).  An evaluation key is long-lived, so this handle keeps its ten
 // base sets in HBM with their window-multiple tables (zkt_g1_bases / zkt_g2_bases), uploads the wire values ONCE per proof and runs the ten sums through the
 // pipelined submit/collect interface; the G1 sets share one group of streams, the G2 sets another (zkt_internal_bases_share_streams: a stream is a hardware queue).
-extern "C" int zkt_internal_bases_share_streams(void* dst, void* src, int share_acc, int tail_base, int tail_span);
 struct zkt_pinocchio_pk {
   size_t n_io = 0, n_mid = 0, max_degree = 0;
   zkt_g1_bases* g1[7] = {};                       // vk, g1_wk, yk, alpha_vk, alpha_wk, alpha_yk, beta_vwy_k (mid)
@@ -337,21 +313,21 @@ int zkt_pinocchio_pk_create(const zkt_pinocchio_crs* c, zkt_pinocchio_pk** out) 
   if (c->n_mid) {
     for (int k = 0; k < 7; ++k) {
       if (!b1[k]) return ZKT_ERR_SHAPE;
-      ZRC(zkt_g1_bases_upload(b1[k], c->n_mid, &pk->g1[k]));
-      if (k) ZRC(zkt_internal_bases_share_streams(pk->g1[k], pk->g1[0], 1, k % 4, 1));      // below 2^19 terms a slot runs its whole MSM on its reduce stream: four side by side
+      ZCHK(zkt_g1_bases_upload(b1[k], c->n_mid, &pk->g1[k]));
+      if (k) ZCHK(zkt_internal_bases_share_streams(pk->g1[k], pk->g1[0], 1, k % 4, 1));      // below 2^19 terms a slot runs its whole MSM on its reduce stream: four side by side
     }
     if (!c->g2_wk_mid) return ZKT_ERR_SHAPE;
-    ZRC(zkt_g2_bases_upload(c->g2_wk_mid, c->n_mid, &pk->g2_wk));
+    ZCHK(zkt_g2_bases_upload(c->g2_wk_mid, c->n_mid, &pk->g2_wk));
   }
   if (c->max_degree) {
     if (!c->si) return ZKT_ERR_SHAPE;
-    ZRC(zkt_g2_bases_upload(c->si, c->max_degree, &pk->si));
-    if (pk->g2_wk) ZRC(zkt_internal_bases_share_streams(pk->si, pk->g2_wk, 1, 2, 1));
+    ZCHK(zkt_g2_bases_upload(c->si, c->max_degree, &pk->si));
+    if (pk->g2_wk) ZCHK(zkt_internal_bases_share_streams(pk->si, pk->g2_wk, 1, 2, 1));
   }
   if (c->n_io) {
     if (!c->wk_io) return ZKT_ERR_SHAPE;
-    ZRC(zkt_g2_bases_upload(c->wk_io, c->n_io, &pk->wk_io));
-    if (pk->g2_wk) ZRC(zkt_internal_bases_share_streams(pk->wk_io, pk->g2_wk, 1, 3, 1));
+    ZCHK(zkt_g2_bases_upload(c->wk_io, c->n_io, &pk->wk_io));
+    if (pk->g2_wk) ZCHK(zkt_internal_bases_share_streams(pk->wk_io, pk->g2_wk, 1, 3, 1));
   }
   if (hipMalloc(&pk->d_wires, (c->n_io + c->n_mid ? c->n_io + c->n_mid : 1) * FRB) != hipSuccess || hipMalloc(&pk->d_h, (c->max_degree ? c->max_degree : 1) * FRB) != hipSuccess) return ZKT_ERR_DEVICE;
   *out = pk.release();
@@ -366,10 +342,10 @@ int zkt_pinocchio_prove_resident(zkt_pinocchio_pk* pk, const uint64_t* wires, co
   std::lock_guard<std::mutex> lk(pk->mu);
   const size_t nio = pk->n_io, nmid = pk->n_mid;
   hipStream_t s = nullptr;
-  QCHK(hipMemcpyAsync(pk->d_wires, wires, (nio + nmid) * FRB, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(pk->d_wires, wires, (nio + nmid) * FRB, hipMemcpyHostToDevice, s));
   // the quotient is padded with zeros to the key's max_degree terms (the resident set has a fixed length; a zero scalar adds nothing)
-  if (h_len) QCHK(hipMemcpyAsync(pk->d_h, h, h_len * FRB, hipMemcpyHostToDevice, s));
-  if (h_len < pk->max_degree) QCHK(hipMemsetAsync((char*)pk->d_h + h_len * FRB, 0, (pk->max_degree - h_len) * FRB, s));
+  if (h_len) HIPCHK(hipMemcpyAsync(pk->d_h, h, h_len * FRB, hipMemcpyHostToDevice, s));
+  if (h_len < pk->max_degree) HIPCHK(hipMemsetAsync((char*)pk->d_h + h_len * FRB, 0, (pk->max_degree - h_len) * FRB, s));
   const uint64_t* d_mid = (const uint64_t*)pk->d_wires + nio * 4;
   // every sum in flight at once; whatever was submitted is collected below even after an error (a slot left pending would block the next proof)
   int rc = ZKT_OK, r2; bool sub1[7] = {}, sub_w = false, sub_h = false, sub_io = false;
@@ -397,19 +373,19 @@ int zkt_pinocchio_prove_resident(zkt_pinocchio_pk* pk, const uint64_t* wires, co
   if (rc_r != ZKT_OK) return rc_r;
   const zkt_g1_affine &sv = sums[0], &sw1 = sums[1], &sy = sums[2], &sav = sums[3], &saw = sums[4], &say = sums[5], &sb = sums[6];
   zkt_g1_affine bsum;
-  ZRC(zkt_g1_add_batch(&rnd[4], &rnd[5], &bsum, 1));
+  ZCHK(zkt_g1_add_batch(&rnd[4], &rnd[5], &bsum, 1));
   zkt_g1_affine lhs[5] = {rnd[0], rnd[1], rnd[2], rnd[3], bsum}, rhs[5] = {sv, sy, sav, say, sb}, out5[5];
-  ZRC(zkt_g1_add_batch(lhs, rhs, out5, 5));
+  ZCHK(zkt_g1_add_batch(lhs, rhs, out5, 5));
   *pf->v_mid_s = out5[0]; *pf->y_mid_s = out5[1]; *pf->alpha_v_mid_s = out5[2]; *pf->alpha_y_mid_s = out5[3]; *pf->beta_vwy_mid_s = out5[4];
   *pf->g1_w_mid_s = sw1; *pf->g2_w_mid_s = sw2; *pf->alpha_w_mid_s = saw;
   // adjusted h(s) (prover.rs:148-161): h_s + w_s delta_v - one_g2 delta_y
   zkt_g2_affine w_s, two[2], muls[2], nody, t2;
-  ZRC(zkt_g2_add_batch(&sw2, &w_io, &w_s, 1));
+  ZCHK(zkt_g2_add_batch(&sw2, &w_io, &w_s, 1));
   two[0] = w_s; two[1] = pk->one_g2;
   uint64_t sc2[8]; memcpy(sc2, delta_v, 32); memcpy(sc2 + 4, delta_y, 32);
-  ZRC(zkt_g2_mul_batch(two, sc2, 4, muls, 2));
-  ZRC(zkt_g2_neg_batch(&muls[1], &nody, 1));
-  ZRC(zkt_g2_add_batch(&h_s, &muls[0], &t2, 1)); ZRC(zkt_g2_add_batch(&t2, &nody, pf->h_s, 1));
+  ZCHK(zkt_g2_mul_batch(two, sc2, 4, muls, 2));
+  ZCHK(zkt_g2_neg_batch(&muls[1], &nody, 1));
+  ZCHK(zkt_g2_add_batch(&h_s, &muls[0], &t2, 1)); ZCHK(zkt_g2_add_batch(&t2, &nody, pf->h_s, 1));
   return ZKT_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "abi.h"
 #include "zkt_internal.h"
 #include "../../include/zkt.h"
+#include "host_abi.h"
 
 namespace zkt {
 
@@ -324,32 +325,6 @@ __global__ void __launch_bounds__(256) k_bytes_mod_r(const uint8_t* __restrict__
 
 using namespace zkt;
 
-namespace {
-struct Dev {   // tiny RAII device buffer.  pooled: stream-ordered on the legacy stream (hipMallocAsync / hipFreeAsync) — for the per-call buffers of the verification entry
-               // points, which run entirely on that stream: a dozen hipMalloc (33-72 us each) and the device-wide wait inside every hipFree were ~0.6 ms of a 4.9 ms verification
-  void* p = nullptr; bool pooled = false;
-  explicit Dev(size_t bytes, bool pool = false) : pooled(pool) {
-    if ((pooled ? hipMallocAsync(&p, bytes ? bytes : 4, nullptr) : hipMalloc(&p, bytes ? bytes : 4)) != hipSuccess) { p = nullptr; (void)hipGetLastError(); }
-  }
-  ~Dev() { if (p) { if (pooled) (void)hipFreeAsync(p, nullptr); else (void)hipFree(p); } }
-  uint32_t* w() const { return (uint32_t*)p; }
-  Dev(const Dev&) = delete; Dev& operator=(const Dev&) = delete;
-};
-#define PCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "[zkt] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); return ZKT_ERR_DEVICE; } } while (0)
-int up(Dev& d, const void* h, size_t bytes, hipStream_t s) { if (!d.p) return ZKT_ERR_DEVICE; if (bytes) PCHK(hipMemcpyAsync(d.p, h, bytes, hipMemcpyHostToDevice, s)); return ZKT_OK; }
-int down(void* h, const void* d, size_t bytes, hipStream_t s) { PCHK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s)); return ZKT_OK; }
-const size_t G1B = sizeof(zkt_g1_affine), G2B = sizeof(zkt_g2_affine), SPB = sizeof(zkt_secp_affine), FRB = 32;
-const uint64_t G1_GEN[13] = {0xfb3af00adb22c6bbull, 0x6c55e83ff97a1aefull, 0xa14e3a3f171bac58ull, 0xc3688c4f9774b905ull, 0x2695638c4fa9ac0full, 0x17f1d3a73197d794ull,
-                             0x0caa232946c5e7e1ull, 0xd03cc744a2888ae4ull, 0x00db18cb2c04b3edull, 0xfcf5e095d5d00af6ull, 0xa09e30ed741d8ae4ull, 0x08b3f481e3aaa0f1ull, 0};   // g1_point.rs:38-47
-const uint64_t G2_GEN[25] = {0xe5ac7d055d042b7eull, 0x334cf11213945d57ull, 0xb5da61bbdc7f5049ull, 0x596bd0d09920b61aull, 0x7dacd3a088274f65ull, 0x13e02b6052719f60ull,
-                             0xd48056c8c121bdb8ull, 0x0bac0326a805bbefull, 0xb4510b647ae3d177ull, 0xc6e47ad4fa403b02ull, 0x260805272dc51051ull, 0x024aa2b2f08f0a91ull,
-                             0xaaa9075ff05f79beull, 0x3f370d275cec1da1ull, 0x267492ab572e99abull, 0xcb3e287e85a763afull, 0x32acd2b02bc28b99ull, 0x0606c4a02ea734ccull,
-                             0xe193548608b82801ull, 0x923ac9cc3baca289ull, 0x6d429a695160d12cull, 0xadfd9baa8cbdd3a7ull, 0x8cc9cdc6da2e351aull, 0x0ce5d527727d6e11ull, 0};   // g2_point.rs:36-46 {x.u1,x.u0,y.u1,y.u0}
-}  // namespace
-
-extern int zkt_internal_ready();   // zkt_api.cpp
-extern void zkt_internal_set_error_index(size_t i);
-
 // Fixed-base tables of a verifying key's statement points (launch_fixed_tables: 64 multiples 16^w P per point, ~3 ms to build), kept for the last few
 // keys seen: a verifier checks many proofs against ONE key, and with the tables the statement sum of a proof is one short launch instead of a 255-step
 // scalar multiplication per wire (4 of the 9 ms of a single verification).  Keyed by the points' bytes; device memory is released with the entry.
@@ -518,36 +493,36 @@ int zkt_groth16_setup(zkt_groth16_crs* c, const uint64_t* ui, const uint64_t* vi
   Dev dP(rows * n * FRB), dtrap(160), due(rows * FRB), dve(rows * FRB), dwe(rows * FRB), dy(rows * FRB), dxp(n * FRB), dxt(n * FRB);
   Dev dgen1(G1B), dgen2(G2B), dout1((rows + 2 * n + 3) * G1B), dout2((n + 3) * G2B), dgt(576), derr(8);
   int rc;
-  if ((rc = up(dtrap, trap, 160, s)) || (rc = up(dgen1, G1_GEN, G1B, s)) || (rc = up(dgen2, G2_GEN, G2B, s))) return rc;
+  if ((rc = up(dtrap, trap, 160, s)) || (rc = up(dgen1, &G1_GEN, G1B, s)) || (rc = up(dgen2, &G2_GEN, G2B, s))) return rc;
   const uint64_t* polys[3] = {ui, vi, wi}; Dev* evals[3] = {&due, &dve, &dwe};
   for (int k = 0; k < 3; ++k) {
     if ((rc = up(dP, polys[k], rows * n * FRB, s))) return rc;
-    hipLaunchKernelGGL(k_poly_eval<FrC>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, (const uint32_t*)dP.w(), rows, n, (const uint32_t*)(dtrap.w() + 32), evals[k]->w());
+    hipLaunchKernelGGL(k_poly_eval<FrC>, dim3(grid_blocks(rows, 64)), dim3(64), 0, s, (const uint32_t*)dP.w(), rows, n, (const uint32_t*)(dtrap.w() + 32), evals[k]->w());
   }
   hipLaunchKernelGGL(k_groth16_setup_scalars, dim3(1), dim3(64), 0, s, (const uint32_t*)due.w(), (const uint32_t*)dve.w(), (const uint32_t*)dwe.w(),
                      (const uint32_t*)dtrap.w(), n, l, m, dy.w(), dxp.w(), dxt.w());
   // fixed-base multiplications g * y (crs.rs:85-135): [uvw (m+1) | xi (n) | xt_by_delta (n) | alpha beta delta]
   uint32_t* o1 = dout1.w();
-  PCHK(launch_generator_mul(G_G1, dgen1.w(), dy.w(), o1, rows, s));
-  PCHK(launch_generator_mul(G_G1, dgen1.w(), dxp.w(), o1 + rows * 26, n, s));
-  PCHK(launch_generator_mul(G_G1, dgen1.w(), dxt.w(), o1 + (rows + n) * 26, n, s));
-  PCHK(launch_generator_mul(G_G1, dgen1.w(), dtrap.w(), o1 + (rows + 2 * n) * 26, 1, s));            // alpha
-  PCHK(launch_generator_mul(G_G1, dgen1.w(), dtrap.w() + 8, o1 + (rows + 2 * n + 1) * 26, 1, s));    // beta
-  PCHK(launch_generator_mul(G_G1, dgen1.w(), dtrap.w() + 24, o1 + (rows + 2 * n + 2) * 26, 1, s));   // delta
+  HIPCHK(launch_generator_mul(G_G1, dgen1.w(), dy.w(), o1, rows, s));
+  HIPCHK(launch_generator_mul(G_G1, dgen1.w(), dxp.w(), o1 + rows * 26, n, s));
+  HIPCHK(launch_generator_mul(G_G1, dgen1.w(), dxt.w(), o1 + (rows + n) * 26, n, s));
+  HIPCHK(launch_generator_mul(G_G1, dgen1.w(), dtrap.w(), o1 + (rows + 2 * n) * 26, 1, s));            // alpha
+  HIPCHK(launch_generator_mul(G_G1, dgen1.w(), dtrap.w() + 8, o1 + (rows + 2 * n + 1) * 26, 1, s));    // beta
+  HIPCHK(launch_generator_mul(G_G1, dgen1.w(), dtrap.w() + 24, o1 + (rows + 2 * n + 2) * 26, 1, s));   // delta
   uint32_t* o2 = dout2.w();
-  PCHK(launch_generator_mul(G_G2, dgen2.w(), dxp.w(), o2, n, s));
-  PCHK(launch_generator_mul(G_G2, dgen2.w(), dtrap.w() + 8, o2 + n * 50, 1, s));          // beta
-  PCHK(launch_generator_mul(G_G2, dgen2.w(), dtrap.w() + 16, o2 + (n + 1) * 50, 1, s));   // gamma
-  PCHK(launch_generator_mul(G_G2, dgen2.w(), dtrap.w() + 24, o2 + (n + 2) * 50, 1, s));   // delta
+  HIPCHK(launch_generator_mul(G_G2, dgen2.w(), dxp.w(), o2, n, s));
+  HIPCHK(launch_generator_mul(G_G2, dgen2.w(), dtrap.w() + 8, o2 + n * 50, 1, s));          // beta
+  HIPCHK(launch_generator_mul(G_G2, dgen2.w(), dtrap.w() + 16, o2 + (n + 1) * 50, 1, s));   // gamma
+  HIPCHK(launch_generator_mul(G_G2, dgen2.w(), dtrap.w() + 24, o2 + (n + 2) * 50, 1, s));   // delta
   unsigned long long noerr = NO_ERR; if ((rc = up(derr, &noerr, 8, s))) return rc;
-  PCHK(launch_tate(o1 + (rows + 2 * n) * 26, o2 + n * 50, dgt.w(), 1, (unsigned long long*)derr.p, s));   // crs.rs:137-139
+  HIPCHK(launch_tate(o1 + (rows + 2 * n) * 26, o2 + n * 50, dgt.w(), 1, (unsigned long long*)derr.p, s));   // crs.rs:137-139
   if ((rc = down(c->g1_uvw_stmt, o1, (l + 1) * G1B, s)) || (rc = down(c->g1_uvw_wit, o1 + (l + 1) * 26, (m - l) * G1B, s)) ||
       (rc = down(c->g1_xi, o1 + rows * 26, n * G1B, s)) || (rc = down(c->g1_xt_by_delta, o1 + (rows + n) * 26, n * G1B, s)) ||
       (rc = down(c->g1_alpha, o1 + (rows + 2 * n) * 26, G1B, s)) || (rc = down(c->g1_beta, o1 + (rows + 2 * n + 1) * 26, G1B, s)) ||
       (rc = down(c->g1_delta, o1 + (rows + 2 * n + 2) * 26, G1B, s)) || (rc = down(c->g2_xi, o2, n * G2B, s)) ||
       (rc = down(c->g2_beta, o2 + n * 50, G2B, s)) || (rc = down(c->g2_gamma, o2 + (n + 1) * 50, G2B, s)) ||
       (rc = down(c->g2_delta, o2 + (n + 2) * 50, G2B, s)) || (rc = down(c->gt_alpha_beta, dgt.p, 576, s))) return rc;
-  PCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   return ZKT_OK;
 }
 
@@ -563,12 +538,12 @@ int zkt_groth16_prove(const zkt_groth16_crs* c, const uint64_t* ui, const uint64
   Dev dP(rows * n * FRB), dw(rows * FRB), dU(n * FRB), dV(n * FRB);
   int rc; if ((rc = up(dw, wires, rows * FRB, s))) return rc;
   if ((rc = up(dP, ui, rows * n * FRB, s))) return rc;
-  hipLaunchKernelGGL(k_lincomb<FrC>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint32_t*)dP.w(), (const uint32_t*)dw.w(), rows, n, dU.w());
+  hipLaunchKernelGGL(k_lincomb<FrC>, dim3(grid_blocks(n)), dim3(256), 0, s, (const uint32_t*)dP.w(), (const uint32_t*)dw.w(), rows, n, dU.w());
   if ((rc = up(dP, vi, rows * n * FRB, s))) return rc;
-  hipLaunchKernelGGL(k_lincomb<FrC>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint32_t*)dP.w(), (const uint32_t*)dw.w(), rows, n, dV.w());
+  hipLaunchKernelGGL(k_lincomb<FrC>, dim3(grid_blocks(n)), dim3(256), 0, s, (const uint32_t*)dP.w(), (const uint32_t*)dw.w(), rows, n, dV.w());
   std::vector<uint64_t> U(n * 4), V(n * 4);
   if ((rc = down(U.data(), dU.p, n * FRB, s)) || (rc = down(V.data(), dV.p, n * FRB, s))) return rc;
-  PCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   zkt_g1_affine sumA, sumB1, sumW, ht; zkt_g2_affine sumB;
   if ((rc = zkt_g1_msm(c->g1_xi, U.data(), n, &sumA)) || (rc = zkt_g2_msm(c->g2_xi, V.data(), n, &sumB)) || (rc = zkt_g1_msm(c->g1_xi, V.data(), n, &sumB1))) return rc;
   if ((rc = zkt_g1_msm(c->g1_uvw_wit, wires + (l + 1) * 4, nw, &sumW)) || (rc = zkt_g1_msm(c->g1_xt_by_delta, h, h_len, &ht))) return rc;
@@ -613,18 +588,18 @@ int zkt_groth16_verify_batch(const zkt_groth16_crs* c, const zkt_g1_affine* A, c
     const std::shared_ptr<void> tabs = stmt_tables_for(c->g1_uvw_stmt, n_stmt, dU.w(), s);     // held until the synchronisation below
     build.tables((const uint32_t*)tabs.get());
     const uint32_t* ate_target = akey ? (const uint32_t*)akey.get() + 2 * (size_t)68 * 84 : nullptr;
-    PCHK(launch_groth16_verify_small(dA.w(), dB.w(), dC.w(), dU.w(), (const uint32_t*)tabs.get(), dW.w(), (int)n_stmt, dg.w(), dd.w(), dab.w(), dtmp.w(), dS.w(), dok.w(), n_proofs, (unsigned long long*)derr.p, s, ate_target));
+    HIPCHK(launch_groth16_verify_small(dA.w(), dB.w(), dC.w(), dU.w(), (const uint32_t*)tabs.get(), dW.w(), (int)n_stmt, dg.w(), dd.w(), dab.w(), dtmp.w(), dS.w(), dok.w(), n_proofs, (unsigned long long*)derr.p, s, ate_target));
     unsigned long long e2 = NO_ERR;
     if ((rc = down(ok, dok.p, n_proofs * 4, s)) || (rc = down(&e2, derr.p, 8, s))) return rc;
-    PCHK(hipStreamSynchronize(s));
+    HIPCHK(hipStreamSynchronize(s));
     if (e2 != NO_ERR) { zkt_internal_set_error_index((size_t)e2); return ZKT_ERR_INFINITY; }
     return ZKT_OK;
   }
   const std::shared_ptr<void> akey = ate_key_now(c, n_stmt, dU.w(), dg.w(), dd.w(), s);      // held until the synchronisation below; null: the value-comparing kernels
-  PCHK(launch_groth16_verify(dA.w(), dB.w(), dC.w(), dU.w(), dW.w(), (int)n_stmt, dg.w(), dd.w(), dab.w(), dok.w(), n_proofs, (unsigned long long*)derr.p, s, (const uint32_t*)akey.get()));
+  HIPCHK(launch_groth16_verify(dA.w(), dB.w(), dC.w(), dU.w(), dW.w(), (int)n_stmt, dg.w(), dd.w(), dab.w(), dok.w(), n_proofs, (unsigned long long*)derr.p, s, (const uint32_t*)akey.get()));
   unsigned long long e = NO_ERR;
   if ((rc = down(ok, dok.p, n_proofs * 4, s)) || (rc = down(&e, derr.p, 8, s))) return rc;
-  PCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   if (e != NO_ERR) { zkt_internal_set_error_index((size_t)e); return ZKT_ERR_INFINITY; }
   return ZKT_OK;
 }
@@ -642,7 +617,7 @@ int zkt_groth16_vk_prepare(const zkt_groth16_crs* c, size_t n_stmt) {
   if ((rc = up(dU, c->g1_uvw_stmt, n_stmt * G1B, s)) || (rc = up(dg, c->g2_gamma, G2B, s)) || (rc = up(dd, c->g2_delta, G2B, s))) return rc;
   const std::shared_ptr<void> akey = ate_key_now(c, n_stmt, dU.w(), dg.w(), dd.w(), s);      // builds the statement points' 16^k tables on its way
   const std::shared_ptr<void> tabs = stmt_tables_for(c->g1_uvw_stmt, n_stmt, dU.w(), s);
-  PCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   return ZKT_OK;
 }
 // single proof: 1 = accept, 0 = reject, negative = -status (a pairing argument at infinity panics in the reference)
@@ -727,7 +702,6 @@ std::shared_ptr<zkt_bp_ipa_ctx> bp_ctx_for(size_t n, const zkt_secp_affine* gg, 
   return sp;
 }
 }  // namespace
-extern "C" void zkt_pinocchio_clear_caches();             // zkt_pinocchio.hip
 extern "C" void zkt_internal_clear_caches() {             // zkt_shutdown: device memory held by the per-key caches
   zkt_pinocchio_clear_caches();
   { std::lock_guard<std::mutex> lk(g_bpc.mu); g_bpc.ctx.reset(); g_bpc.key.clear(); }
@@ -749,14 +723,14 @@ int zkt_bp_ipa_ctx_create(size_t n, const zkt_secp_affine* gg, const zkt_secp_af
   std::unique_ptr<zkt_bp_ipa_ctx> c(new zkt_bp_ipa_ctx(n));
   if (!c->ok()) return ZKT_ERR_DEVICE;
   const size_t N = n;
-  PCHK(hipMemcpyAsync(c->dbase.p, gg, N * SPB, hipMemcpyDefault, s));                        // host or device pointers (the range proof hands over hh' in HBM)
-  PCHK(hipMemcpyAsync((char*)c->dbase.p + N * SPB, hh, N * SPB, hipMemcpyDefault, s));
-  PCHK(hipMemcpyAsync((char*)c->dbase.p + 2 * N * SPB, u, SPB, hipMemcpyDefault, s));
+  HIPCHK(hipMemcpyAsync(c->dbase.p, gg, N * SPB, hipMemcpyDefault, s));                        // host or device pointers (the range proof hands over hh' in HBM)
+  HIPCHK(hipMemcpyAsync((char*)c->dbase.p + N * SPB, hh, N * SPB, hipMemcpyDefault, s));
+  HIPCHK(hipMemcpyAsync((char*)c->dbase.p + 2 * N * SPB, u, SPB, hipMemcpyDefault, s));
   c->side.assign((c->levels + zkt_bp_ipa_ctx::IPA_BATCH - 1) / zkt_bp_ipa_ctx::IPA_BATCH, nullptr);
-  for (hipStream_t& x : c->side) PCHK(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
-  PCHK(hipEventCreateWithFlags(&c->ev, hipEventDisableTiming));
-  PCHK(hipEventCreateWithFlags(&c->ev_null, hipEventDisableTiming));
-  PCHK(hipStreamCreateWithFlags(&c->main, hipStreamNonBlocking));
+  for (hipStream_t& x : c->side) HIPCHK(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
+  HIPCHK(hipEventCreateWithFlags(&c->ev, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&c->ev_null, hipEventDisableTiming));
+  HIPCHK(hipStreamCreateWithFlags(&c->main, hipStreamNonBlocking));
   int rc = zkt_secp_bases_from_device((const zkt_secp_affine*)c->dbase.p, c->NB, s, &c->set);
   if (rc) return rc;
   *out = c.release();
@@ -773,16 +747,16 @@ static int ipa_verdict_submit(zkt_bp_ipa_ctx* c, const uint64_t* a, const uint64
   if (hipMemcpyAsync(AL, a, N * FRB, hipMemcpyDefault, s) != hipSuccess || hipMemcpyAsync(BL, b, N * FRB, hipMemcpyDefault, s) != hipSuccess) return ZKT_ERR_DEVICE;
   int rc2;
   if ((rc2 = up(c->dx, xs, levels * FRB, s))) return rc2;
-  hipLaunchKernelGGL(k_ipa_challenges_all, dim3((unsigned)((levels + 63) / 64)), dim3(64), 0, s, (const uint32_t*)c->dx.w(), (int)levels, CH);
+  hipLaunchKernelGGL(k_ipa_challenges_all, dim3(grid_blocks(levels, 64)), dim3(64), 0, s, (const uint32_t*)c->dx.w(), (int)levels, CH);
   size_t lv = 0;
   for (; lv < levels && (N >> lv) > 2048; ++lv) {
     const size_t np = (N >> lv) / 2, o = 2 * N - ((2 * N) >> lv), o2 = 2 * N - ((2 * N) >> (lv + 1));
-    hipLaunchKernelGGL(k_ipa_fold_ab, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, (const uint32_t*)(AL + o * 8), (const uint32_t*)(BL + o * 8), (const uint32_t*)(CH + lv * 32), np,
+    hipLaunchKernelGGL(k_ipa_fold_ab, dim3(grid_blocks(np)), dim3(256), 0, s, (const uint32_t*)(AL + o * 8), (const uint32_t*)(BL + o * 8), (const uint32_t*)(CH + lv * 32), np,
                        AL + o2 * 8, BL + o2 * 8);
   }
   if (lv < levels) hipLaunchKernelGGL(k_ipa_fold_tail, dim3(1), dim3(1024), 0, s, AL, BL, (const uint32_t*)CH, N, (int)lv, (int)levels);
   uint32_t* sF = c->dsc.w() + (size_t)slot * NB * 8;            // the slot's scalar buffer
-  hipLaunchKernelGGL(k_ipa_verdict_scalars, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const uint32_t*)AL, (const uint32_t*)BL, (const uint32_t*)CH, wH0, N, (int)levels, sF);
+  hipLaunchKernelGGL(k_ipa_verdict_scalars, dim3(grid_blocks(N)), dim3(256), 0, s, (const uint32_t*)AL, (const uint32_t*)BL, (const uint32_t*)CH, wH0, N, (int)levels, sF);
   hipLaunchKernelGGL(k_ipa_u_dots, dim3((unsigned)(2 * levels), IPA_DOT_SPLIT), dim3(256), 0, s, (const uint32_t*)AL, (const uint32_t*)BL, (const uint32_t*)CH, N, c->dpart.w());
   hipLaunchKernelGGL(k_ipa_u_scalar, dim3(1), dim3(64), 0, s, (const uint32_t*)AL, (const uint32_t*)BL, (const uint32_t*)c->dpart.w(), N, (int)levels, sF);
   if (hipGetLastError() != hipSuccess) return ZKT_ERR_DEVICE;
@@ -820,7 +794,7 @@ static int ipa_run(zkt_bp_ipa_ctx* c, const zkt_secp_affine* P, const uint64_t* 
   if (hipMemcpyAsync(da.p, a, N * FRB, hipMemcpyDefault, s) != hipSuccess || hipMemcpyAsync(db.p, b, N * FRB, hipMemcpyDefault, s) != hipSuccess ||
       hipMemcpyAsync(dPp.p, P, SPB, hipMemcpyDefault, s) != hipSuccess) return -ZKT_ERR_DEVICE;                                  // P, a, b: host or device
   if ((rc = up(dx, xs, levels * FRB, s))) return -rc;
-  const unsigned gN = (unsigned)((N + 256) / 256);            // N + 1 threads
+  const unsigned gN = grid_blocks(N + 1);                      // N + 1 threads
   hipLaunchKernelGGL(k_ipa_w_init, dim3(gN), dim3(256), 0, s, N, wH0, dwG.w(), dwH.w());
   uint32_t *Av = da.w(), *Bv = db.w(), *A2 = da2.w(), *B2 = db2.w();
   std::vector<zkt_secp_affine> lr(2 * levels + 1);            // L_0, R_0, L_1, R_1, ..., base-case right-hand side
@@ -861,18 +835,18 @@ static int ipa_run(zkt_bp_ipa_ctx* c, const zkt_secp_affine* P, const uint64_t* 
     // x, x^-1, x^2, x^-2; generator coefficients and a' = a_lo x + a_hi x^-1 ; b' = b_lo x^-1 + b_hi x   (:44-45, :49-50)
     hipLaunchKernelGGL(k_ipa_challenge, dim3(1), dim3(64), 0, s, (const uint32_t*)(dx.w() + level * 8), dch.w(), dsq.w() + level * 16);
     const uint32_t *X = dch.w(), *XI = dch.w() + 8;
-    if (!out_trace) hipLaunchKernelGGL(k_ipa_comb, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, s, (const uint32_t*)slot_buf(m), (const uint32_t*)slot_buf(m + 1),
+    if (!out_trace) hipLaunchKernelGGL(k_ipa_comb, dim3(grid_blocks(NB)), dim3(256), 0, s, (const uint32_t*)slot_buf(m), (const uint32_t*)slot_buf(m + 1),
                                        (const uint32_t*)(dch.w() + 16), (const uint32_t*)(dch.w() + 24), NB, level == 0 ? 1 : 0, c->dcomb.w());
     hipLaunchKernelGGL(k_ipa_w_fold, dim3(gN), dim3(256), 0, s, X, XI, N, n, dwG.w(), dwH.w());
-    hipLaunchKernelGGL(k_fold<SnC>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, (const uint32_t*)Av, (const uint32_t*)(Av + np * 8), X, XI, np, A2);
-    hipLaunchKernelGGL(k_fold<SnC>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, (const uint32_t*)Bv, (const uint32_t*)(Bv + np * 8), XI, X, np, B2);
+    hipLaunchKernelGGL(k_fold<SnC>, dim3(grid_blocks(np)), dim3(256), 0, s, (const uint32_t*)Av, (const uint32_t*)(Av + np * 8), X, XI, np, A2);
+    hipLaunchKernelGGL(k_fold<SnC>, dim3(grid_blocks(np)), dim3(256), 0, s, (const uint32_t*)Bv, (const uint32_t*)(Bv + np * 8), XI, X, np, B2);
     std::swap(Av, A2); std::swap(Bv, B2);
     n = np; ++level;
   }
   // base case (:28-32): c = a*b; rhs = g*a + h*b + u*c over the original generators
   if ((rc = free_slot(n_msm - 1))) return -rc;
   hipLaunchKernelGGL(k_ipa_final_scalars, dim3(gN), dim3(256), 0, s, (const uint32_t*)Av, (const uint32_t*)Bv, (const uint32_t*)dwG.w(), (const uint32_t*)dwH.w(), N, slot_buf(n_msm - 1));
-  if (!out_trace && levels) hipLaunchKernelGGL(k_ipa_sub, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, s, (const uint32_t*)c->dcomb.w(), NB, slot_buf(n_msm - 1));
+  if (!out_trace && levels) hipLaunchKernelGGL(k_ipa_sub, dim3(grid_blocks(NB)), dim3(256), 0, s, (const uint32_t*)c->dcomb.w(), NB, slot_buf(n_msm - 1));
   if (hipGetLastError() != hipSuccess) return -ZKT_ERR_DEVICE;
   if ((rc = submit(n_msm - 1))) return -rc;
   while (collected < n_msm) if ((rc = collect_next())) return -rc;
@@ -1003,7 +977,7 @@ static int range_proof_core(zkt_bp_ipa_ctx* c, const zkt_secp_affine* V, const u
   auto slot = [&](int k) { return c->dsc.w() + (size_t)k * NB * 8; };
   uint32_t *l = newv(), *r = newv(), *yinv_n = newv();
   uint32_t* sums = news(); for (int q = 1; q < 7; ++q) (void)news();                 // seven consecutive scalars
-  const size_t nblk = (n + 255) / 256;
+  const size_t nblk = grid_blocks(n);
   hipLaunchKernelGGL(k_rp_fused<SnC>, dim3((unsigned)nblk), dim3(256), 0, s, (const uint32_t*)d_aL, (const uint32_t*)d_sL, (const uint32_t*)d_sR,
                      RpScalars{y, yinv, z, z2, x}, n, RpOut{slot(0), slot(1), slot(2), slot(3), use_ipa ? nullptr : slot(4), l, r, yinv_n, dparts7.w()});
   hipLaunchKernelGGL(k_rp_sums<SnC>, dim3(7), dim3(256), 0, s, (const uint32_t*)dparts7.w(), nblk, sums);
@@ -1124,9 +1098,9 @@ int zkt_pairing_product_check_batch(const zkt_g1_affine* g1, const zkt_g2_affine
   if (!dok.p) return ZKT_ERR_DEVICE;
   PairArgs a{};
   for (size_t j = 0; j < k; ++j) { a.g1[j] = d1.w() + j * 26; a.g2[j] = d2.w() + j * 50; a.s1[j] = (uint32_t)(k * 26); a.s2[j] = (uint32_t)(k * 50); a.neg[j] = negate && negate[j]; }
-  PCHK(launch_pairing_product_check(a, (int)k, dok.w(), n, (unsigned long long*)derr.p, s));
+  HIPCHK(launch_pairing_product_check(a, (int)k, dok.w(), n, (unsigned long long*)derr.p, s));
   if ((rc = down(ok, dok.p, n * 4, s)) || (rc = down(&e, derr.p, 8, s))) return rc;
-  PCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   if (e != NO_ERR) { zkt_internal_set_error_index((size_t)e); return ZKT_ERR_INFINITY; }
   return ZKT_OK;
 }
@@ -1138,12 +1112,12 @@ static int bls_hash_dev(const uint8_t* msgs, const uint64_t* offsets, size_t n, 
   const size_t total = (size_t)offsets[n];
   Dev dm(total), doff((n + 1) * 8), dsc(n * FRB), dgen2(G2B), derr(8);
   int rc;
-  if ((rc = up(dm, msgs, total, s)) || (rc = up(doff, offsets, (n + 1) * 8, s)) || (rc = up(dgen2, G2_GEN, G2B, s))) return rc;
+  if ((rc = up(dm, msgs, total, s)) || (rc = up(doff, offsets, (n + 1) * 8, s)) || (rc = up(dgen2, &G2_GEN, G2B, s))) return rc;
   if (!dsc.p || !dH.p || !derr.p) return ZKT_ERR_DEVICE;
-  hipLaunchKernelGGL(k_bytes_mod_r, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint8_t*)dm.p, (const unsigned long long*)doff.p, n, dsc.w());
-  if (times) PCHK(launch_fp_op(F_FR, OP_MUL, dsc.w(), times, dsc.w(), n, (unsigned long long*)derr.p, s));      // inputs are reduced mod r first, as PrimeFieldElem::new does
-  PCHK(launch_generator_mul(G_G2, dgen2.w(), dsc.w(), dH.w(), n, s));
-  PCHK(hipStreamSynchronize(s));
+  hipLaunchKernelGGL(k_bytes_mod_r, dim3(grid_blocks(n)), dim3(256), 0, s, (const uint8_t*)dm.p, (const unsigned long long*)doff.p, n, dsc.w());
+  if (times) HIPCHK(launch_fp_op(F_FR, OP_MUL, dsc.w(), times, dsc.w(), n, (unsigned long long*)derr.p, s));      // inputs are reduced mod r first, as PrimeFieldElem::new does
+  HIPCHK(launch_generator_mul(G_G2, dgen2.w(), dsc.w(), dH.w(), n, s));
+  HIPCHK(hipStreamSynchronize(s));
   return ZKT_OK;
 }
 int zkt_bls_hash_to_g2_batch(const uint8_t* msgs, const uint64_t* offsets, size_t n, zkt_g2_affine* out) {
@@ -1153,7 +1127,7 @@ int zkt_bls_hash_to_g2_batch(const uint8_t* msgs, const uint64_t* offsets, size_
   hipStream_t s = nullptr; Dev dH(n * G2B);
   int rc = bls_hash_dev(msgs, offsets, n, dH, s); if (rc) return rc;
   if ((rc = down(out, dH.p, n * G2B, s))) return rc;
-  PCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   return ZKT_OK;
 }
 // Signer::gen_public_key (signature.rs:24-27): G1 generator * sk
@@ -1163,11 +1137,11 @@ int zkt_bls_public_keys_batch(const uint64_t* sks, size_t n, zkt_g1_affine* pks)
   if (n == 0) return ZKT_OK;
   hipStream_t s = nullptr; Dev dsk(n * FRB), dgen1(G1B), dpk(n * G1B);
   int rc;
-  if ((rc = up(dsk, sks, n * FRB, s)) || (rc = up(dgen1, G1_GEN, G1B, s))) return rc;
+  if ((rc = up(dsk, sks, n * FRB, s)) || (rc = up(dgen1, &G1_GEN, G1B, s))) return rc;
   if (!dpk.p) return ZKT_ERR_DEVICE;
-  PCHK(launch_generator_mul(G_G1, dgen1.w(), dsk.w(), dpk.w(), n, s));
+  HIPCHK(launch_generator_mul(G_G1, dgen1.w(), dsk.w(), dpk.w(), n, s));
   if ((rc = down(pks, dpk.p, n * G1B, s))) return rc;
-  PCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   return ZKT_OK;
 }
 // Signer::sign (signature.rs:28-31): hash_to_g2point(m) * sk
@@ -1180,7 +1154,7 @@ int zkt_bls_sign_batch(const uint8_t* msgs, const uint64_t* offsets, const uint6
   if ((rc = up(dsk, sks, n * FRB, s))) return rc;
   if ((rc = bls_hash_dev(msgs, offsets, n, dsig, s, dsk.w()))) return rc;      // (h * sk) G2 = sk * hash_to_g2point(m): the hash point has order r
   if ((rc = down(sigs, dsig.p, n * G2B, s))) return rc;
-  PCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   return ZKT_OK;
 }
 // Signer::verify (signature.rs:34-39): tate(g1, sig) == tate(pk, hash_to_g2point(m)), one signature per lane as the
@@ -1191,15 +1165,15 @@ int zkt_bls_verify_batch(const uint8_t* msgs, const uint64_t* offsets, const zkt
   if (n == 0) return ZKT_OK;
   hipStream_t s = nullptr; Dev dH(n * G2B), dsig(n * G2B), dpk(n * G1B), dgen1(G1B), dok(n * 4), derr(8);
   int rc = bls_hash_dev(msgs, offsets, n, dH, s); if (rc) return rc;
-  if ((rc = up(dsig, sigs, n * G2B, s)) || (rc = up(dpk, pks, n * G1B, s)) || (rc = up(dgen1, G1_GEN, G1B, s))) return rc;
+  if ((rc = up(dsig, sigs, n * G2B, s)) || (rc = up(dpk, pks, n * G1B, s)) || (rc = up(dgen1, &G1_GEN, G1B, s))) return rc;
   unsigned long long noerr = NO_ERR, e = NO_ERR; if ((rc = up(derr, &noerr, 8, s))) return rc;
   if (!dok.p) return ZKT_ERR_DEVICE;
   PairArgs a{};
   a.g1[0] = dgen1.w(); a.s1[0] = 0; a.g2[0] = dsig.w(); a.s2[0] = 50; a.neg[0] = 0;
   a.g1[1] = dpk.w(); a.s1[1] = 26; a.g2[1] = dH.w(); a.s2[1] = 50; a.neg[1] = 1;
-  PCHK(launch_pairing_product_check(a, 2, dok.w(), n, (unsigned long long*)derr.p, s, 1u));      // slot 0's P is the G1 generator (signature.rs:36)
+  HIPCHK(launch_pairing_product_check(a, 2, dok.w(), n, (unsigned long long*)derr.p, s, 1u));      // slot 0's P is the G1 generator (signature.rs:36)
   if ((rc = down(ok, dok.p, n * 4, s)) || (rc = down(&e, derr.p, 8, s))) return rc;
-  PCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   if (e != NO_ERR) { zkt_internal_set_error_index((size_t)e); return ZKT_ERR_INFINITY; }
   return ZKT_OK;
 }

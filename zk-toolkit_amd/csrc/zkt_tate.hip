@@ -91,7 +91,7 @@ static hipError_t count_marks(const uint32_t* out, size_t n, hipStream_t s, uint
   uint32_t* d = nullptr; hipError_t e;
   if ((e = hipMallocAsync((void**)&d, 8, s)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(d, 0, 8, s)) != hipSuccess) { (void)hipFreeAsync(d, s); return e; }
-  hipLaunchKernelGGL(k_count_marks, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, d);
+  hipLaunchKernelGGL(k_count_marks, dim3(grid_blocks(n)), dim3(256), 0, s, out, n, d);
   if ((e = hipMemcpyAsync(host, d, 8, hipMemcpyDeviceToHost, s)) != hipSuccess) { (void)hipFreeAsync(d, s); return e; }
   if ((e = hipFreeAsync(d, s)) != hipSuccess) return e;
   return hipStreamSynchronize(s);
@@ -106,18 +106,18 @@ hipError_t launch_tate(const uint32_t* g1, const uint32_t* g2, uint32_t* out, si
     if ((e = hipMallocAsync((void**)&flags, n * sizeof(uint32_t), s)) != hipSuccess) return e;
     if ((e = guard_fork(s, &side)) != hipSuccess || (e = launch_short_loop_guards(a, 1, flags, n, side)) != hipSuccess ||
         (e = launch_dtate(g1, g2, out, n, err, TATE_MARK_WORD, TATE_MARK_EXACT, s)) != hipSuccess || (e = guard_join(s, side)) != hipSuccess) { (void)hipFreeAsync(flags, s); return e; }
-    hipLaunchKernelGGL(k_tate_resolve, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const uint32_t*)flags, g1, g2, out, n);
+    hipLaunchKernelGGL(k_tate_resolve, dim3(grid_blocks(n, 64)), dim3(64), 0, s, (const uint32_t*)flags, g1, g2, out, n);
     if ((e = hipFreeAsync(flags, s)) != hipSuccess) return e;
   } else {
-    hipLaunchKernelGGL(k_tate, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, g1, g2, out, n, err);
+    hipLaunchKernelGGL(k_tate, dim3(grid_blocks(n, 64)), dim3(64), 0, s, g1, g2, out, n, err);
   }
   hipError_t e; uint32_t marks[2] = {0, 0};
   if ((e = hipGetLastError()) != hipSuccess || (e = count_marks(out, n, s, marks)) != hipSuccess) return e;
   if (marks[0]) {                                           // Q on E' outside G2 somewhere: the 255-step loop for those elements (it may hand some on)
-    hipLaunchKernelGGL(k_tate_long_marked, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, g1, g2, out, n, err);
+    hipLaunchKernelGGL(k_tate_long_marked, dim3(grid_blocks(n, 64)), dim3(64), 0, s, g1, g2, out, n, err);
     if ((e = hipGetLastError()) != hipSuccess || (e = count_marks(out, n, s, marks)) != hipSuccess) return e;
   }
-  if (marks[1]) hipLaunchKernelGGL(k_tate_exact_marked, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, g1, g2, out, n, err);
+  if (marks[1]) hipLaunchKernelGGL(k_tate_exact_marked, dim3(grid_blocks(n, 64)), dim3(64), 0, s, g1, g2, out, n, err);
   return hipGetLastError();
 }
 
