@@ -1,0 +1,199 @@
+"""Bulletproofs on the GPU (zkt_protocols.hip: range proof and inner-product argument over secp256k1) compared bit for bit with the
+discrete-log model of tests/bp_model.py at every size whose code path differs, up to 2^17.  The verdict alone cannot see every error:
+wrong but self-consistent y^i / y^-i sequences leave (65), (66-67), (68) and the argument true, and only the output points show it,
+so every case compares A, S, T1, T2, P (range proof) and L, R, P' of every level (traced argument) with the model.
+
+The sizes and the paths they reach (launch lines in zkt_protocols.hip):
+  n = 1        no IPA level: ipa_run takes the traced form even without a trace (`!out_trace && levels >= 1` fails); k_rp_fused, one block
+  n = 2        one level: k_ipa_fold_tail folds it (ipa_verdict_submit), one IPA_BATCH group of one level (ipa_run collect_next)
+  n = 32, 128  5 and 7 levels: the last IPA_BATCH (4) group is short (5 = 4 + 1, 7 = 4 + 3); 11 and 15 MSMs wrap the IPA_SLOTS (8) slots
+  n = 256      k_rp_fused in one block of 256 (range_proof_core); nblk = 1 for k_rp_sums
+  n = 512      k_rp_fused in two blocks: k_rp_sums folds two per-block parts
+  n = 2048     k_ipa_fold_tail does every level in one block (ipa_verdict_submit: N >> lv > 2048 never holds)
+  n = 4096     the first k_ipa_fold_ab launch (level 0), then the tail
+  n = 65536    the benchmarked size (bench.py, BASELINE config 5): 256 k_rp_fused blocks, 5 k_ipa_fold_ab levels
+  n = 131072   nblk = 512 > 256: each k_rp_sums thread folds two parts (its `b += 256` loop); 6 k_ipa_fold_ab levels"""
+import copy, ctypes, importlib
+import numpy as np
+import pytest
+from zkt_testlib import ptr, int_to_limbs, SECP_N, SECP_GEN, py_secp_mul, secp_arr
+import bp_model as M
+
+pytestmark = pytest.mark.gpu
+zk = importlib.import_module("zk-toolkit_amd")
+
+SMALL = (1, 2, 32, 128, 256, 512, 2048, 4096)
+LARGE = (65536, 131072)
+LARGE_KINDS = ("honest", "nonbit_vstar")      # the honest proof, and the only accepting input that takes the "some other V" product
+
+
+@pytest.fixture(scope="module")
+def L():
+    zk.init()
+    return zk.lib()
+
+
+class DevGens:
+    """2n + 3 generators k·G made on the device from known ks (zkt_secp_mul_batch), 64 of them checked against python integers"""
+
+    def __init__(self, L, n, seed):
+        cnt = 2 * n + 3
+        ks = M.scalars(seed, cnt)
+        pts = np.zeros((cnt, 9), np.uint64)
+        zk.check(L.zkt_secp_mul_batch(ptr(np.repeat(secp_arr([SECP_GEN]), cnt, axis=0)), ptr(ks), 4, ptr(pts), cnt))
+        k = M.ints(ks)
+        for i in sorted(set(np.linspace(0, cnt - 1, 64).astype(int))):
+            assert (pts[i] == secp_arr([py_secp_mul(SECP_GEN, k[i])])[0]).all(), f"generator {i}"
+        self.G = M.Gens(k[2 * n], k[2 * n + 1], k[2 * n + 2], k[:n], k[n:2 * n])
+        self.gg, self.hh = pts[:n].copy(), pts[n:2 * n].copy()
+        self.g, self.h, self.u = pts[2 * n:2 * n + 1].copy(), pts[2 * n + 1:2 * n + 2].copy(), pts[2 * n + 2:].copy()
+
+    def with_gh(self, g, h, kg, kh):
+        """the same gg, hh, u with other g, h (dlogs kg, kh)"""
+        o = copy.copy(self)
+        o.G = M.Gens(kg, kh, self.G.u, self.G.gg, self.G.hh)
+        o.g, o.h = g, h
+        return o
+
+
+_gens = {}
+
+
+def gens(L, n):
+    if n not in _gens:
+        _gens[n] = DevGens(L, n, 5000 + n)
+    return _gens[n]
+
+
+def ctx_create(L, D, n):
+    c = ctypes.c_void_p()
+    zk.check(L.zkt_bp_ipa_ctx_create(n, ptr(D.gg), ptr(D.hh), ptr(D.u), ctypes.byref(c)))
+    return c
+
+
+def check_range_proof(L, D, n, I, ctx, tag):
+    """one instance through zkt_bp_range_proof and zkt_bp_range_proof_ctx (ctx over D's gg, hh, u), both use_ipa values"""
+    Vd = I.V(D.G)
+    V = M.points([Vd])
+    for use_ipa in (0, 1):
+        ok, pts = M.range_proof(n, Vd, I.aLi, I.gammai, D.G, I.rndi, use_ipa, I.xsi)
+        want = M.points(pts)
+        for entry in ("one-shot", "ctx"):
+            got = np.zeros((5, 9), np.uint64)
+            if entry == "one-shot":
+                v = L.zkt_bp_range_proof(n, ptr(V), ptr(I.aL), ptr(I.gamma), ptr(D.g), ptr(D.h), ptr(D.gg), ptr(D.hh), use_ipa, ptr(I.rnd), ptr(D.u), ptr(I.xs), ptr(got))
+            else:
+                v = L.zkt_bp_range_proof_ctx(ctx, ptr(V), ptr(I.aL), ptr(I.gamma), ptr(D.g), ptr(D.h), use_ipa, ptr(I.rnd), ptr(I.xs), ptr(got))
+            where = f"{tag} n={n} {I.kind} use_ipa={use_ipa} {entry}"
+            assert v == int(ok), f"{where}: verdict {v}, reference {int(ok)}"
+            for j, name in enumerate(("A", "S", "T1", "T2", "P")):
+                assert (got[j] == want[j]).all(), f"{where}: {name}"
+    return ok
+
+
+@pytest.mark.parametrize("n,kind", [(n, k) for n in SMALL for k in M.KINDS] + [(n, k) for n in LARGE for k in LARGE_KINDS])
+def test_range_proof_vs_model(L, n, kind):
+    D = gens(L, n)
+    I = M.rp_instance(kind, n, 100 * n + M.KINDS.index(kind))
+    ctx = ctx_create(L, D, n)
+    try:
+        assert check_range_proof(L, D, n, I, ctx, "range proof") == M.EXPECT[kind]
+    finally:
+        L.zkt_bp_ipa_ctx_free(ctx)
+
+
+def _ipa_calls(L, D, n, ctx, P, a, b, xs, lv):
+    """(verdict, trace) of the traced and (verdict, None) of the verdict-only form, through the one-shot entry and the context"""
+    out = {}
+    for entry in ("one-shot", "ctx"):
+        for traced in (True, False):
+            tr = np.zeros((max(3 * lv, 1), 9), np.uint64) if traced else None
+            if entry == "one-shot":
+                v = L.zkt_bp_inner_product_argument(n, ptr(D.gg), ptr(D.hh), ptr(D.u), ptr(P), ptr(a), ptr(b), ptr(xs), ptr(tr))
+            else:
+                v = L.zkt_bp_inner_product_argument_ctx(ctx, ptr(P), ptr(a), ptr(b), ptr(xs), ptr(tr))
+            out[(entry, traced)] = (v, tr)
+    return out
+
+
+def _check_ipa(L, D, n, ctx, P, ai, a, b, I, name):
+    lv = M.levels_of(n) if n > 1 else 0
+    ok, trace = M.ipa(n, D.G.gg, D.G.hh, D.G.u, P, ai, I.bi, I.xsi)
+    want = M.points(trace) if lv else None
+    for (entry, traced), (v, tr) in _ipa_calls(L, D, n, ctx, M.points([P]), a, b, I.xs, lv).items():
+        where = f"ipa n={n} {name} {entry} {'traced' if traced else 'verdict-only'}"
+        assert v == int(ok), f"{where}: verdict {v}, reference {int(ok)}"
+        if traced and lv:
+            for j in range(lv):
+                for q, nm in enumerate(("L", "R", "P'")):
+                    assert (tr[3 * j + q] == want[3 * j + q]).all(), f"{where}: {nm} of level {j}"
+    return ok
+
+
+@pytest.mark.parametrize("n", SMALL + LARGE)
+def test_ipa_vs_model(L, n):
+    import torch
+    D = gens(L, n)
+    I = M.ipa_instance(n, 7 * n + 1, D.G)
+    ctx = ctx_create(L, D, n)
+    try:
+        assert _check_ipa(L, D, n, ctx, I.P, I.ai, I.a, I.b, I, "honest")
+        for j in sorted({0, n // 2 - 1, n // 2, n - 1} - {-1}):         # one coefficient of a changed
+            a2 = I.a.copy(); ai2 = list(I.ai); ai2[j] = (ai2[j] + 1) % SECP_N; a2[j] = int_to_limbs(ai2[j], 4)
+            assert not _check_ipa(L, D, n, ctx, I.P, ai2, a2, I.b, I, f"a[{j}] + 1")
+        assert not _check_ipa(L, D, n, ctx, (I.P + D.G.u) % SECP_N, I.ai, I.a, I.b, I, "P + u")
+        # P, a, b as device tensors (the header allows device pointers for a context), and a context made from device generators
+        lv = M.levels_of(n) if n > 1 else 0
+        ok, trace = M.ipa(n, D.G.gg, D.G.hh, D.G.u, I.P, I.ai, I.bi, I.xsi)
+        dev = lambda arr: torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).cuda()
+        dP, da, db = dev(M.points([I.P])), dev(I.a), dev(I.b)
+        dgg, dhh, du = dev(D.gg), dev(D.hh), dev(D.u)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        torch.cuda.synchronize()
+        c2 = ctypes.c_void_p()
+        zk.check(L.zkt_bp_ipa_ctx_create(n, vp(dgg), vp(dhh), vp(du), ctypes.byref(c2)))
+        try:
+            for c in (ctx, c2):
+                tr = np.zeros((max(3 * lv, 1), 9), np.uint64)
+                assert L.zkt_bp_inner_product_argument_ctx(c, vp(dP), vp(da), vp(db), ptr(I.xs), ptr(tr)) == int(ok)
+                if lv: assert (tr[:3 * lv] == M.points(trace)).all(), f"ipa n={n}: device P, a, b: trace"
+                assert L.zkt_bp_inner_product_argument_ctx(c, vp(dP), vp(da), vp(db), ptr(I.xs), None) == int(ok)
+        finally:
+            L.zkt_bp_ipa_ctx_free(c2)
+    finally:
+        L.zkt_bp_ipa_ctx_free(ctx)
+
+
+def test_fixed_tables_follow_g_and_h(L):
+    """One context, proofs with (g1, h1), then (g2, h2), then (g1, h1) again: the fixed-base tables of g and h are rebuilt whenever
+    the point differs from the one they were built for (range_proof_core's same_point)."""
+    n = 32
+    D1 = gens(L, n)
+    k2 = M.scalars(77, 2); k2i = M.ints(k2)
+    gh2 = np.zeros((2, 9), np.uint64)
+    zk.check(L.zkt_secp_mul_batch(ptr(np.repeat(secp_arr([SECP_GEN]), 2, axis=0)), ptr(k2), 4, ptr(gh2), 2))
+    D2 = D1.with_gh(gh2[0:1].copy(), gh2[1:2].copy(), k2i[0], k2i[1])
+    assert (D2.g == M.points([k2i[0]])).all() and (D2.h == M.points([k2i[1]])).all()
+    ctx = ctx_create(L, D1, n)
+    try:
+        for step, D in enumerate((D1, D2, D1)):
+            for kind in ("honest", "nonbit_vstar"):
+                I = M.rp_instance(kind, n, 900 + 10 * step + M.KINDS.index(kind))
+                assert check_range_proof(L, D, n, I, ctx, f"g/h set {step}") == M.EXPECT[kind]
+    finally:
+        L.zkt_bp_ipa_ctx_free(ctx)
+
+
+def test_one_shot_cache_follows_generators(L):
+    """One-shot calls at one n with generator set A, then B, then A: bp_ctx_for keys its cached context by the bytes of gg, hh, u."""
+    n = 256
+    A, B = gens(L, n), DevGens(L, n, 6100)
+    for step, D in enumerate((A, B, A)):
+        I = M.rp_instance("honest", n, 950 + step)
+        c = ctx_create(L, D, n)
+        try:
+            assert check_range_proof(L, D, n, I, c, f"generator set {'ABA'[step]}")
+            J = M.ipa_instance(n, 960 + step, D.G)
+            assert _check_ipa(L, D, n, c, J.P, J.ai, J.a, J.b, J, f"generator set {'ABA'[step]}")
+        finally:
+            L.zkt_bp_ipa_ctx_free(c)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 from zkt_testlib import *
 from qap_util import chain_circuit_sparse, sparse_struct, alloc_crs, groth16_proof_scalars
+import bp_model
 
 pytestmark = pytest.mark.gpu
 zk = importlib.import_module("zk-toolkit_amd")
@@ -272,6 +273,12 @@ def test_config5_range_proof_65536_bits(L):
         assert (pts_a == pts_b).all()                                            # A, S, T1, T2, P identical through both entry points
         assert L.zkt_bp_range_proof_ctx(rctx, ptr(V), ptr(bad), ptr(gamma), ptr(g_r), ptr(h_r), use_ipa, ptr(rnd), ptr(xs), None) == 0
     L.zkt_bp_ipa_ctx_free(rctx)
+    # A, S, T1, T2, P bit for bit: every generator's dlog is known (ks), so the discrete-log model (tests/bp_model.py) gives them in python integers
+    K = _ints(ks)
+    G = bp_model.Gens(K[2 * n + 1], K[2 * n + 2], K[2 * n], K[:n], K[n:2 * n])
+    gam, rndi, xsi = _ints(gamma)[0], _ints(rnd), _ints(xs)
+    ok, want = bp_model.range_proof(n, (G.g * value + G.h * gam) % SECP_N, bits, gam, G, rndi, 1, xsi)
+    assert ok and (pts_a == bp_model.points(want)).all(), "A, S, T1, T2, P at 65,536 bits"
     # inner-product argument alone at 65,536 generators, resident generators: accept, and reject after one coefficient changes
     a, b = rand_u64_array(12, (n, 4)), rand_u64_array(13, (n, 4))
     a[:, 3] >>= np.uint64(1); b[:, 3] >>= np.uint64(1)
@@ -283,6 +290,9 @@ def test_config5_range_proof_65536_bits(L):
     trace = np.zeros((16 * 3, 9), np.uint64)                                        # with a trace: the level-by-level form (32 L/R MSMs), same verdict
     assert L.zkt_bp_inner_product_argument_ctx(ctx, ptr(P), ptr(a), ptr(b), ptr(xs), ptr(trace)) == 1
     assert (trace[:, 8] == 0).all()
+    ai, bi = _ints(a), _ints(b)
+    ok, want = bp_model.ipa(n, G.gg, G.hh, G.u, (bp_model.dot(G.gg, ai) + bp_model.dot(G.hh, bi) + G.u * c) % SECP_N, ai, bi, xsi)
+    assert ok and (trace == bp_model.points(want)).all(), "L, R, P' of all 16 levels at 65,536 generators"
     a2 = a.copy(); a2[123, 0] ^= np.uint64(1)
     assert L.zkt_bp_inner_product_argument_ctx(ctx, ptr(P), ptr(a2), ptr(b), ptr(xs), None) == 0
     L.zkt_bp_ipa_ctx_free(ctx)
