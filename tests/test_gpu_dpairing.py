@@ -78,7 +78,10 @@ def test_large_batch_kernels_still_covered_in_a_forced_process():
     """Small batches now take the lane-distributed kernels, so the one-element-per-lane kernels (k_tate, k_groth16_verify_ate with the key's line and
     statement tables — the chain circuit's statement is a full-size field element —, k_pairing_product_check_ate and the older kernels behind them)
     would only be reached by the 2^16-element tests.  Re-run the small parity tests of every pairing consumer in ONE
-    child process with the switch-over forced to zero (ZKT_DTATE_MAX = ZKT_DPRODUCT_MAX = 0): same oracle, other kernels."""
+    child process with the switch-over forced to zero (ZKT_DTATE_MAX = ZKT_DPRODUCT_MAX = 0): same oracle, other kernels.
+    tests/test_gpu_pairing_routes.py now reaches k_tate, k_pairing_product_check_ate and the large Groth16 routes at their default switch-over, with
+    every element class; this test still covers what that module does not: the protocols' own callers (Pinocchio's fall-back when the small-batch
+    kernels refuse, the chain circuit's full-size statement, keys made by zkt_groth16_setup) on those kernels."""
     import os, subprocess, sys
     env = dict(os.environ, ZKT_DTATE_MAX="0", ZKT_DPRODUCT_MAX="0", ZKT_MSM_GRAPH="0")      # ... and the small MSMs of these protocols issued launch by launch, not as graph replays
     here = os.path.dirname(os.path.abspath(__file__))

@@ -416,6 +416,12 @@ int ate_key_begin(const zkt_groth16_crs* c, size_t n_stmt, const uint32_t* dU, c
     if (e.stamp && e.key == kb) return -1;                            // someone else got there first
     if (e.state == 0 && (!victim || e.stamp < victim->stamp)) victim = &e;
   }
+  if (!victim) {                                                      // every entry still waits for its verdict (state 2 until a lookup of ITS key settles it): settle
+    for (AteKey& e : g_ate) {                                         // them here, or four keys seen once each would hold the cache for the rest of the process
+      ate_settle_locked(e);
+      if (e.state == 0 && (!victim || e.stamp < victim->stamp)) victim = &e;
+    }
+  }
   if (!victim) return -1;
   AteKey& e = *victim;
   if (!g_ate_side && hipStreamCreateWithFlags(&g_ate_side, hipStreamNonBlocking) != hipSuccess) { g_ate_side = nullptr; (void)hipGetLastError(); return -1; }
