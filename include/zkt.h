@@ -387,7 +387,10 @@ int zkt_secp_jac_sum_dev(const uint32_t* dev_partials, size_t count, void* strea
  * points take the R1CS itself, one sparse row per constraint (R1CS.constraints, r1cs.rs; Constraint{a,b,c},
  * constraint.rs:5-9; SparseVec), and produce the SAME proof points: setup derives device-resident Lagrange-basis
  * bases from the trapdoor, prove is 3 sparse mat-vecs + Fr NTTs + three MSMs whose outputs are A, B, C.
- * rowptr: n+1 offsets into col/val; col: wire index 0..m; val: 4-limb canonical Fr. */
+ * rowptr: n+1 offsets into col/val; col: wire index 0..m; val: 4-limb canonical Fr.
+ * n is at most ZKT_R1CS_MAX_N = 2^21 - 1 constraints (setup forms the 2n + 1 factorials by a prefix product of at most 2048^2 elements);
+ * a larger n is ZKT_ERR_SHAPE before anything is allocated or launched. */
+#define ZKT_R1CS_MAX_N 2097151
 typedef struct { const uint64_t* rowptr; const uint32_t* col; const uint64_t* val; } zkt_sparse_rows;
 typedef struct zkt_groth16_pk zkt_groth16_pk;
 /* CRS::new (crs.rs:49-146) with injected trapdoors.  Fills the verifying part of `vk` (g1_alpha, g1_beta, g1_delta,

@@ -256,21 +256,15 @@ def qap_util_pin_ek(): return list(_PIN_EK)
 def qap_util_pin_vk(): return list(_PIN_VK)
 
 
-def groth16_proof_scalars(mats, wires, l, trap, r, s):
-    """The discrete logarithms of a Groth16 proof's (A, B, C) in python integers, O(n + nnz): with the trapdoor known,
-         A = (alpha + a(x) + r delta) G1,   B = (beta + b(x) + s delta) G2,
-         C = ((beta U_wit + alpha V_wit + W_wit + a(x) b(x) - c(x)) / delta + s A + r B - r s delta) G1      (prover.rs:96-147, crs.rs:65-121)
-       where a(x) = sum_j (A w)_j L_j(x) over the Lagrange basis of {1..n} (qap.rs:33-97), U_wit = the same with the witness columns only, and
-       h(x) t(x) = a(x) b(x) - c(x) for a satisfying witness (prover.rs:64-71).  One batch inversion for the n values x - j.
-       mats: three CSR triples (rowptr, col, val[nnz,4] u64); wires: (m+1, 4) u64; trap = [alpha, beta, gamma, delta, x] as 1x4 u64 arrays.
-       Independent of the HIP path AND of the oracle."""
-    from zkt_testlib import R
-    to_int = lambda a: [int.from_bytes(np.ascontiguousarray(row).tobytes(), "little") for row in np.asarray(a).reshape(-1, 4)]
-    alpha, beta, gamma, delta, x = (to_int(t)[0] for t in trap)
-    r, s = to_int(r)[0], to_int(s)[0]
-    w = to_int(wires)
-    n = len(mats[0][0]) - 1
-    # L_j(x) = t(x) / ((x - j) t'(j)),  t'(j) = (-1)^(n-j) (j-1)! (n-j)!
+def _to_ints(a):
+    """(k, 4) u64 limbs -> k python ints"""
+    b = np.ascontiguousarray(a, dtype=np.uint64).tobytes()
+    return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
+
+
+def lagrange_at(n, x):
+    """L_j(x), j = 1..n, the Lagrange basis of {1..n} at x (qap.rs:33-97) in O(n): L_j(x) = t(x) / ((x - j) t'(j)), t'(j) = (-1)^(n-j) (j-1)! (n-j)!,
+       with one batch inversion for the n values x - j and one for the n denominators.  x in {1..n} is the caller's error (t(x) = 0)."""
     fact = [1] * (n + 1)
     for k in range(1, n + 1): fact[k] = fact[k - 1] * k % R
     d = [(x - j) % R for j in range(1, n + 1)]
@@ -294,21 +288,140 @@ def groth16_proof_scalars(mats, wires, l, trap, r, s):
         inv_run = inv_run * den[j] % R
         v = tx * dinv[j] % R * di % R
         Lx[j] = v if (n - (j + 1)) % 2 == 0 else (R - v) % R
-    def evals(M):
-        rowptr, col, val = M
-        rp = [int(v) for v in rowptr]; cl = [int(c) for c in col]; vl = to_int(val)
-        full = wit = 0
-        for j in range(n):
-            fj = wj = 0
-            for k in range(rp[j], rp[j + 1]):
-                t = vl[k] * w[cl[k]]
-                fj += t
-                if cl[k] > l: wj += t
-            full += fj % R * Lx[j]; wit += wj % R * Lx[j]
-        return full % R, wit % R
-    (a, U), (b, V), (c, W) = evals(mats[0]), evals(mats[1]), evals(mats[2])
+    return Lx
+
+
+def row_dots(mats, wires, l):
+    """(A w)_j, (B w)_j, (C w)_j and the same over the witness columns i > l only, per constraint: three pairs of object arrays of python ints mod R"""
+    w = np.array(_to_ints(wires) + [0], dtype=object)
+    out = []
+    for rowptr, col, val in mats:
+        n = len(rowptr) - 1; nnz = int(rowptr[n])
+        rp = rowptr.astype(np.int64); c = col[:nnz].astype(np.int64)
+        prods = np.concatenate([np.array(_to_ints(val[:nnz]), dtype=object) * w[c], np.array([0], dtype=object)])
+        wprods = np.where(np.concatenate([c > l, [False]]), prods, 0)
+        empty = rp[1:] == rp[:-1]
+        def sums(p):
+            v = np.add.reduceat(p, rp[:-1]) % R if n else np.zeros(0, dtype=object)
+            v[empty] = 0
+            return v
+        out.append((sums(prods), sums(wprods)))
+    return out
+
+
+def groth16_proof_scalars(mats, wires, l, trap, r, s, Lx=None, rows=None):
+    """The discrete logarithms of a Groth16 proof's (A, B, C) in python integers, O(n + nnz): with the trapdoor known,
+         A = (alpha + a(x) + r delta) G1,   B = (beta + b(x) + s delta) G2,
+         C = ((beta U_wit + alpha V_wit + W_wit + a(x) b(x) - c(x)) / delta + s A + r B - r s delta) G1      (prover.rs:96-147, crs.rs:65-121)
+       where a(x) = sum_j (A w)_j L_j(x) over the Lagrange basis of {1..n} (qap.rs:33-97), U_wit = the same with the witness columns only, and
+       h(x) t(x) = a(x) b(x) - c(x) for a satisfying witness (prover.rs:64-71).
+       mats: three CSR triples (rowptr, col, val[nnz,4] u64); wires: (m+1, 4) u64; trap = [alpha, beta, gamma, delta, x] as 1x4 u64 arrays.
+       Lx = lagrange_at(n, x) and rows = row_dots(...) may come from the caller (the first n entries are used).  Independent of the HIP path AND of the oracle."""
+    alpha, beta, gamma, delta, x = (_to_ints(t)[0] for t in trap)
+    r, s = _to_ints(r)[0], _to_ints(s)[0]
+    n = len(mats[0][0]) - 1
+    if Lx is None: Lx = lagrange_at(n, x)
+    if rows is None: rows = row_dots(mats, wires, l)
+    L = np.array(Lx[:n], dtype=object)
+    (a, U), (b, V), (c, W) = [tuple(int(np.dot(v[:n], L)) % R if n else 0 for v in pair) for pair in rows]
     As = (alpha + a + r * delta) % R
     Bs = (beta + b + s * delta) % R
     dinv_ = pow(delta, -1, R)
     Cs = ((beta * U + alpha * V + W + a * b - c) * dinv_ + s * As + r * Bs - r * s * delta) % R
     return As, Bs, Cs
+
+
+def uvw_stmt_scalars(mats, l, trap, Lx=None):
+    """the discrete logarithms of vk.g1_uvw_stmt: (beta u_i(x) + alpha v_i(x) + w_i(x)) / gamma for the statement wires i = 0..l (crs.rs:66-84),
+       u_i(x) = sum_j A[j][i] L_j(x).  A statement wire in no constraint gets 0, i.e. the point at infinity."""
+    alpha, beta, gamma, delta, x = (_to_ints(t)[0] for t in trap)
+    n = len(mats[0][0]) - 1
+    if Lx is None: Lx = lagrange_at(n, x)
+    L = np.array(list(Lx[:n]) + [0], dtype=object)
+    ev = []
+    for rowptr, col, val in mats:
+        nnz = int(rowptr[n])
+        ks = np.nonzero(col[:nnz] <= l)[0]
+        rows = np.searchsorted(rowptr.astype(np.int64), ks, side="right") - 1
+        prods = np.array(_to_ints(val[ks]), dtype=object) * L[rows]
+        cs = col[ks]
+        ev.append([int(prods[cs == i].sum()) for i in range(l + 1)])
+    gi = pow(gamma, -1, R)
+    return [(beta * u + alpha * v + w_) * gi % R for u, v, w_ in zip(*ev)]
+
+
+LONG_ROWS_AT = 4098          # asym_circuit_sparse(long_rows=True): rows 4098 and 4099 are the long ones
+
+
+def asym_circuit_sparse(n, seed=7, l=3, long_rows=False, unused_stmt=False, unused_wit=False, all_public=False):
+    """A sparse R1CS whose A and B differ, with a satisfying witness by construction: constraint j defines a new wire v_j through
+         (A_j w) (B_j w) = c_j v_j,
+       A_j one to four terms, B_j the "one" wire and up to three more, all over wires defined before j's layer (rows 2^(k-1) .. 2^k - 1 form layer k),
+       with random coefficients throughout; the "one" column of B has a term in every constraint.
+       Wires: [one | l statement inputs | two witness inputs | (a witness wire in no constraint) | v_0 .. v_{n-1}].
+       long_rows: rows 4098 and 4099 of A hold 4096 and 4097 terms, of B 4097 and 4096 (present in every n >= 4100).
+       unused_stmt: statement wire l is in no constraint; unused_wit: one witness wire is in no constraint.  all_public: l = m.
+       The first n' constraints, with the wires they use, are a satisfied circuit of n' constraints with the same layout (prefix()).
+       Returns ((A, B, C) CSR triples, wires (m+1, 4) u64, l, m) like chain_circuit_sparse."""
+    assert l >= 1 and (not long_rows or n >= LONG_ROWS_AT + 2)
+    g = np.random.default_rng(seed)
+    nfree = 2
+    used0 = np.array([i for i in range(l + 1) if not (unused_stmt and i == l)] + [l + 1 + k for k in range(nfree)])
+    base = l + 1 + nfree + (1 if unused_wit else 0)                  # wire of v_0
+    m = base + n - 1
+    p0 = len(used0)
+    to_wire = lambda u: np.where(u < p0, used0[np.minimum(u, p0 - 1)], base + u - p0)
+    j = np.arange(n, dtype=np.int64)
+    layer0 = np.where(j > 0, np.left_shift(1, np.frexp(j.astype(np.float64))[1].astype(np.int64) - 1), 0)    # first row of j's layer
+    avail = p0 + layer0                                              # usable wires of row j: used0 and v_0 .. v_{layer0 - 1}
+
+    def rows(first_one, sizes):
+        k = g.integers(1, 5, size=n)
+        u = (g.random((n, 4)) * avail[:, None]).astype(np.int64)
+        if first_one: u[:, 0] = 0                                    # index 0 of used0 is the "one" wire
+        ok = np.arange(4)[None, :] < k[:, None]
+        for t in range(1, 4):                                        # no wire twice in a row
+            for t2 in range(t): ok[:, t] &= u[:, t] != u[:, t2]
+        if long_rows:                                                # rows LONG_ROWS_AT and LONG_ROWS_AT + 1 replaced by `sizes` distinct wires each
+            tail = [to_wire(np.sort(g.choice(avail[LONG_ROWS_AT + q], size=sz, replace=False))) for q, sz in enumerate(sizes)]
+            head, rest = ok[:LONG_ROWS_AT], ok[LONG_ROWS_AT + 2:]
+            col = np.concatenate([to_wire(u[:LONG_ROWS_AT][head])] + tail + [to_wire(u[LONG_ROWS_AT + 2:][rest])])
+            lens = np.concatenate([head.sum(1), [len(x) for x in tail], rest.sum(1)])
+        else:
+            col = to_wire(u[ok]); lens = ok.sum(1)
+        rp = np.zeros(n + 1, np.int64); rp[1:] = np.cumsum(lens)
+        return rp, col
+    rpA, colA = rows(False, (4096, 4097)); rpB, colB = rows(True, (4097, 4096))
+    top = np.uint64(R >> 192)
+    def coeffs(k):
+        v = g.integers(0, 1 << 64, size=(k, 4), dtype=np.uint64, endpoint=False)
+        v[:, 3] %= top; v[:, 0] |= np.uint64(1)                      # < R, never zero
+        return v
+    valA, valB, valC = coeffs(len(colA)), coeffs(len(colB)), coeffs(n)
+    # the witness, one layer after the other (a layer only reads wires of earlier layers)
+    w = np.empty(m + 1, dtype=object); w[:base] = [1] + _to_ints(coeffs(base - 1))
+    va, vb, vc = (np.array(_to_ints(v), dtype=object) for v in (valA, valB, valC))
+    pre = [1] * (n + 1)                                              # 1 / c_j by one batch inversion
+    for q in range(n): pre[q + 1] = pre[q] * vc[q] % R
+    inv_run = pow(pre[n], -1, R) if n else 1; cinv = np.empty(n, dtype=object)
+    for q in range(n - 1, -1, -1):
+        cinv[q] = inv_run * pre[q] % R; inv_run = inv_run * vc[q] % R
+    j0 = 0
+    while j0 < n:
+        j1 = min(n, max(1, 2 * j0))
+        def dots(rp, col, v):
+            k0, k1 = rp[j0], rp[j1]
+            return np.add.reduceat(v[k0:k1] * w[col[k0:k1]], rp[j0:j1] - k0) % R
+        w[base + j0:base + j1] = dots(rpA, colA, va) * dots(rpB, colB, vb) % R * cinv[j0:j1] % R
+        j0 = j1
+    mats = ((rpA.astype(np.uint64), colA.astype(np.uint32), valA), (rpB.astype(np.uint64), colB.astype(np.uint32), valB),
+            (np.arange(n + 1, dtype=np.uint64), (base + np.arange(n)).astype(np.uint32), valC))
+    return mats, ints_to_arr(list(w), 4), (m if all_public else l), m
+
+
+def prefix(circuit, n):
+    """the first n constraints of an asym_circuit_sparse circuit and the wires they use: the circuit of n"""
+    mats, wires, l, m = circuit
+    nw0 = m + 1 - (len(mats[0][0]) - 1)                              # wires before v_0
+    cut = lambda rp, col, val: (rp[:n + 1].copy(), col[:int(rp[n])].copy(), val[:int(rp[n])].copy())
+    return tuple(cut(*M) for M in mats), wires[:nw0 + n].copy(), (nw0 + n - 1 if l == m else l), nw0 + n - 1

@@ -6,6 +6,7 @@ from zkt_testlib import R, SplitMix64
 import numpy as np
 from zkt_testlib import ints_to_arr
 from qap_util import example_cubic, chain_circuit, chain_circuit_sparse, qap_from_r1cs, domain_model, groth16_proof_scalars
+from r1cs_plan_model import block_plan as _block_plan
 
 
 def _eval(p, x):
@@ -47,18 +48,6 @@ def test_proof_scalars_in_linear_time_equal_the_coefficient_form(n):
     assert got == (As, Bs, Cs)
 
 
-def _block_plan(n, nshards, shard):
-    """The host arithmetic of zkt_groth16_setup_r1cs_sharded (csrc/zkt_groth16_r1cs.hip): this rank's range of the n - 1 quotient values and its block sizes."""
-    tot = n - 1 if n >= 2 else 0
-    base, extra = tot // nshards, tot % nshards
-    lo = shard * base + min(shard, extra); hi = lo + base + (1 if shard < extra else 0)
-    cnt, s0 = hi - lo, lo + 1
-    logM = 1
-    while (1 << (logM - 1)) < cnt or (logM <= 10 and (1 << (logM - 1)) < n): logM += 1
-    M = 1 << logM; Bi = M // 2; Q = (n + Bi - 1) // Bi if cnt else 1
-    return cnt, s0, Bi, M, Q
-
-
 @pytest.mark.parametrize("n,nshards", [(2, 1), (5, 1), (37, 1), (1025, 1), (1500, 1), (1500, 3), (2600, 5), (2600, 8), (40, 39)])
 def test_blocked_convolution_gives_every_rank_its_quotient_values(n, nshards):
     """k_recip_blocks / k_prep_blocks / k_sum_blocks in python integers: S(s) = sum_{j=1..n} f_j / (n + s - j) for the rank's s = s0 .. s0 + cnt - 1 equals entry s - s0 of
@@ -89,3 +78,69 @@ def test_blocked_convolution_gives_every_rank_its_quotient_values(n, nshards):
             assert got % R == want, (shard, u)
         seen += cnt
     assert seen == max(n - 1, 0)                                      # the ranks' ranges tile s = 1 .. n-1
+
+
+def _dense(M, n, cols):
+    rowptr, col, val = M
+    vals = [int.from_bytes(np.ascontiguousarray(v).tobytes(), "little") for v in val]
+    D = [[0] * cols for _ in range(n)]
+    for j in range(n):
+        for k in range(int(rowptr[j]), int(rowptr[j + 1])): D[j][int(col[k])] = (D[j][int(col[k])] + vals[k]) % R
+    return D
+
+
+@pytest.mark.parametrize("n,opts", [(1, {}), (2, {"l": 1}), (7, {"unused_stmt": True, "unused_wit": True}), (12, {"l": 4}), (9, {"all_public": True}),
+                                    ("40:13", {"unused_wit": True})])
+def test_asymmetric_circuit_and_its_models_equal_the_coefficient_form(n, opts):
+    """qap_util.asym_circuit_sparse is satisfied by its witness, its A and B differ, and the python-integer models the GPU plan tests check against —
+    groth16_proof_scalars over row_dots and uvw_stmt_scalars (vk.g1_uvw_stmt) — equal the reference's coefficient-form prover and CRS (prover.rs:96-147,
+    crs.rs:65-121) over the dense QAP.  "40:13": the first 13 constraints of a 40-constraint circuit (qap_util.prefix)."""
+    from qap_util import asym_circuit_sparse, prefix, row_dots, uvw_stmt_scalars, lagrange_at
+    if isinstance(n, str):
+        big, n = (int(v) for v in n.split(":"))
+        mats, wires, l, m = prefix(asym_circuit_sparse(big, seed=big, **opts), n)
+    else:
+        mats, wires, l, m = asym_circuit_sparse(n, seed=n, **opts)
+    toi = lambda a: [int.from_bytes(np.ascontiguousarray(v).tobytes(), "little") for v in np.asarray(a).reshape(-1, 4)]
+    wit = toi(wires)
+    assert len(wit) == m + 1 and l == (m if opts.get("all_public") else opts.get("l", 3))
+    A, B, C = (_dense(M, n, m + 1) for M in mats)
+    dot = lambda D: [sum(c * w for c, w in zip(row, wit)) % R for row in D]
+    assert [a * b % R for a, b in zip(dot(A), dot(B))] == dot(C), "witness does not satisfy the circuit"
+    if n > 1: assert A != B
+    for k, flag in ((l, "unused_stmt"), (l + 3, "unused_wit")):
+        if opts.get(flag): assert all(row[k] == 0 for D in (A, B, C) for row in D)
+    rows = row_dots(mats, wires, l)
+    assert [list(v) for v in rows[0]] == [dot(A), [sum(c * w for c, w in list(zip(row, wit))[l + 1:]) % R for row in A]]
+    rng = SplitMix64(77 + n); fr = lambda v: ints_to_arr([v], 4)
+    trap = [fr(rng.below(R - 1) + 1) for _ in range(5)]; r = fr(rng.below(R - 1) + 1); s = fr(rng.below(R - 1) + 1)
+    alpha, beta, gamma, delta, x = [toi(t)[0] for t in trap]
+    rr, ss = toi(r)[0], toi(s)[0]
+    ui, vi, wi, h, t = qap_from_r1cs(A, B, C, wit)
+    As = (alpha + sum(wit[i] * _eval(ui[i], x) for i in range(m + 1)) + rr * delta) % R
+    Bs = (beta + sum(wit[i] * _eval(vi[i], x) for i in range(m + 1)) + ss * delta) % R
+    di = pow(delta, -1, R)
+    Cs = (sum(wit[i] * (beta * _eval(ui[i], x) + alpha * _eval(vi[i], x) + _eval(wi[i], x)) for i in range(l + 1, m + 1)) * di
+          + _eval(h, x) * _eval(t, x) * di + ss * As + rr * Bs - rr * ss * delta) % R
+    Lx = lagrange_at(n, x)
+    assert groth16_proof_scalars(mats, wires, l, trap, r, s) == (As, Bs, Cs)
+    assert groth16_proof_scalars(mats, wires, l, trap, r, s, Lx=Lx, rows=rows) == (As, Bs, Cs)
+    gi = pow(gamma, -1, R)
+    want = [(beta * _eval(ui[i], x) + alpha * _eval(vi[i], x) + _eval(wi[i], x)) * gi % R for i in range(l + 1)]
+    assert uvw_stmt_scalars(mats, l, trap) == want == uvw_stmt_scalars(mats, l, trap, Lx=Lx)
+    if opts.get("unused_stmt"): assert want[l] == 0
+
+
+def test_asymmetric_circuit_long_rows():
+    """long_rows: rows 4098 and 4099 of A hold 4096 and 4097 terms, of B 4097 and 4096, every wire once, and the witness still satisfies every row"""
+    from qap_util import asym_circuit_sparse, row_dots, LONG_ROWS_AT
+    n = LONG_ROWS_AT + 9
+    mats, wires, l, m = asym_circuit_sparse(n, seed=5, long_rows=True)
+    for (rowptr, col, _), want in zip(mats[:2], ((4096, 4097), (4097, 4096))):
+        lens = np.diff(rowptr.astype(np.int64))
+        assert tuple(lens[LONG_ROWS_AT:LONG_ROWS_AT + 2]) == want and lens.max() == 4097 and (lens[:LONG_ROWS_AT] <= 4).all()
+        for j in (LONG_ROWS_AT, LONG_ROWS_AT + 1):
+            c = col[int(rowptr[j]):int(rowptr[j + 1])]
+            assert len(set(c.tolist())) == len(c) and c.max() < l + 3 + j
+    (az, _), (bz, _), (cz, _) = row_dots(mats, wires, l)
+    assert list(az * bz % R) == list(cz)

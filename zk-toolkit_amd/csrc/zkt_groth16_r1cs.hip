@@ -427,7 +427,7 @@ int zkt_groth16_setup_r1cs_sharded(size_t n, size_t l, size_t m, const zkt_spars
                                    size_t shard, size_t nshards, zkt_groth16_crs* vk, zkt_groth16_pk** out) {
   if (zkt_internal_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
   if (nshards == 0 || shard >= nshards || nshards > n) return ZKT_ERR_SHAPE;
-  if (!A || !B || !Cmat || !alpha || !beta || !gamma || !delta || !x || !vk || !out || n == 0 || l > m || n >= (1ull << 30)) return ZKT_ERR_SHAPE;
+  if (!A || !B || !Cmat || !alpha || !beta || !gamma || !delta || !x || !vk || !out || n == 0 || l > m || n > ZKT_R1CS_MAX_N) return ZKT_ERR_SHAPE;   // 2n + 1 factorials: two levels of scan tiles
   if (!A->rowptr || !B->rowptr || !Cmat->rowptr) return ZKT_ERR_SHAPE;
   uint64_t trap[20]; memcpy(trap, alpha, 32); memcpy(trap + 4, beta, 32); memcpy(trap + 8, gamma, 32); memcpy(trap + 12, delta, 32); memcpy(trap + 16, x, 32);
   for (int k = 0; k < 5; ++k) { bool z = true; for (int j = 0; j < 4; ++j) z = z && trap[4 * k + j] == 0; if (z) return ZKT_ERR_INV_ZERO; }   // rand_elem(true): non-zero (crs.rs:59-63)
