@@ -11,7 +11,7 @@
  * Data layout (all little-endian, plain arrays of uint64_t, caller-owned):
  *   Fq   6 limbs, canonical residue in [0,q)      (PrimeFieldElem.e, prime_field_elem.rs:263-272)
  *   Fr   4 limbs, canonical residue in [0,r)
- *   scalars for point multiplication: `scalar_limbs` limbs each (4 or 6), used as-is,
+ *   scalars for point multiplication: `scalar_limbs` limbs each (1 to 6; anything else is ZKT_ERR_SHAPE), used as-is,
  *        NOT reduced mod r (macros.rs:10-21)
  *   Fq2  {u1,u0} (fq2.rs:16-19) = 12 limbs; Fq6 {v2,v1,v0} (fq6.rs:16-20) = 36 limbs;
  *   Fq12 {w1,w0} (fq12.rs:18-21) = 72 limbs = the order of the tests' to_strs (fq12.rs:179-195)
@@ -169,7 +169,8 @@ int zkt_secp_mul_batch(const zkt_secp_affine* points, const uint64_t* scalars, i
 /* a18 (vector forms of the group): AffinePoints::sum secp256k1/affine_points.rs:25-31 — the fold from AffinePoint::zero(), so n = 0 gives the point
  * at infinity — and AffinePoints * PrimeFieldElem :105-122, every point times ONE scalar k (scalar_limbs u64 limbs, used as-is like a8).  The
  * element-wise point-vector + point-vector (:84-103) and point-vector * scalar-vector (:124-144) are *_add_batch / *_mul_batch above; the same calls
- * exist for G1 and G2. */
+ * exist for G1 and G2.  The library adds in a tree, not in the fold's order: for points of ONE curve y^2 = x^3 + b' (any b', so every honest input) the
+ * chord-and-tangent rule is associative, sums are order-independent and hence equal to the fold; the same holds for the zkt_*_msm calls below. */
 int zkt_g1_sum(const zkt_g1_affine* points, size_t n, zkt_g1_affine* out);
 int zkt_g2_sum(const zkt_g2_affine* points, size_t n, zkt_g2_affine* out);
 int zkt_secp_sum(const zkt_secp_affine* points, size_t n, zkt_secp_affine* out);

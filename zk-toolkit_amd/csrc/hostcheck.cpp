@@ -4,6 +4,7 @@
 // this, and the C ABI in include/zkt.h has no CPU path.  Built by __graft_entry__.build()
 // as zk-toolkit_amd/libzkt_hostcheck.so (hipcc --cuda-host-only).
 #include "abi.h"
+#include <vector>
 #include "fq_program.h"
 using namespace zkt;
 
@@ -166,3 +167,137 @@ int zkt_hostcheck_ate_product(int kv, int kf, const uint32_t* g1, const uint32_t
   return odd;
 }
 }
+
+// ---- whole batches, for the case lists of tests/prim_cases.py (tests/test_prim_cases.py) ------------------------------------------------------------
+// The 8-word branch of k_fp_op (zkt_field.hip) REPEATED, not shared: canonical values in and out (fp_canon32, then fp_mul(fp_mul(x, y), R^2); the inverse of x R), where
+// zkt_hostcheck_fp goes through ld_fp / st_fp.  tests/test_prim_cases.py compares the two texts between the marker comments after stripping whitespace.
+// op: 0 add 1 sub 2 mul 3 sqr 4 neg 5 inv 7 cube (the numbering of zkt_hostcheck_fp).  Returns the lowest index whose inverse was asked of zero, or -1.
+template <class C> static long fp_canon_run(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
+  enum { OP_ADD = 0, OP_SUB = 1, OP_MUL = 2, OP_SQR = 3, OP_NEG = 4, OP_INV = 5, OP_CUBE = 7 };
+  long first = -1;
+  // `atomicMin`, `err` and `OP` exist under these names ONLY so that the kernel's text below compiles here unchanged (the device has the HIP intrinsic, an error
+  // word in memory and a template parameter); the loop body keeps the kernel's indentation for the same reason: the text comparison ignores white space only.
+  auto atomicMin = [](long* e, unsigned long long i) { if (*e < 0 || (long)i < *e) *e = (long)i; };
+  long* err = &first;
+  const int OP = op;
+  for (size_t i = 0; i < n; ++i) {
+  // canonical 32-bit-limb fields: any 256-bit input is first reduced mod the order, as PrimeFieldElem::new does (prime_field_elem.rs:263-272)
+  Fp<C> x = fp_canon32(ld_raw<C>(a + i * C::N)), r, r2;
+  for (int j = 0; j < C::N; ++j) r2.v[j] = C::r2(j);
+  if (OP == OP_ADD) r = fp_add(x, fp_canon32(ld_raw<C>(b + i * C::N)));          // canonical in, canonical out
+  else if (OP == OP_SUB) r = fp_sub(x, fp_canon32(ld_raw<C>(b + i * C::N)));
+  else if (OP == OP_NEG) r = fp_neg(x);
+  else if (OP == OP_MUL) r = fp_mul(fp_mul(x, fp_canon32(ld_raw<C>(b + i * C::N))), r2);     // (a b R^-1) R^2 R^-1 = a b
+  else if (OP == OP_SQR) r = fp_mul(fp_mul(x, x), r2);
+  else if (OP == OP_CUBE) { Fp<C> xm = fp_mul(x, r2); r = fp_mul(fp_mul(xm, xm), x); }        // (xR)(xR)/R = x^2 R;  x^2 R * x / R = x^3
+  else {                                                             // safe_inv: Err on zero (prime_field_elem.rs:379-382)
+    if (fp_is_zero(x)) { atomicMin(err, (unsigned long long)i); r = x; }
+    else {
+      Fp<C> one = fp_zero<C>(); one.v[0] = 1;
+      r = fp_mul(fp_inv(fp_mul(x, r2)), one);
+    }
+  }
+  st_raw<C>(out + i * C::N, r);
+  }
+  return first;
+}
+extern "C" {
+long zkt_hostcheck_fp_canon(int field, int op, const uint32_t* a, const uint32_t* b, uint32_t* o, size_t n) {
+  switch (field) { case 1: return fp_canon_run<FrC>(op, a, b, o, n); case 2: return fp_canon_run<SpC>(op, a, b, o, n); case 3: return fp_canon_run<SnC>(op, a, b, o, n); }
+  return -2;                                                            // Fq is a lazy-limb field: zkt_hostcheck_fp is its kernel's sequence
+}
+// the kernels' own zero test on the loaded value (k_fp_op, W = 28 branch: fp_is_zero after ld_fp): the lowest index holding zero, or -1
+long zkt_hostcheck_fp_first_zero(int field, const uint32_t* a, size_t n) {
+  auto run = [&](auto tag) -> long { typedef decltype(tag) C; for (size_t i = 0; i < n; ++i) if (fp_is_zero(ld_fp<C>(a + i * C::ABI_N))) return (long)i; return -1; };
+  switch (field) { case 0: return run(FqC{}); case 1: return run(FrC{}); case 2: return run(SpC{}); default: return run(SnC{}); }
+}
+// the other field kernels of zkt_field.hip on whole batches: op 0 pow (k_fp_pow: e_words 32-bit words per exponent, shared != 0: one exponent for every element),
+// 1 scale (k_fp_scale: b = one factor), 2 sum (the fold of fp_add from zero that k_fp_sum's lanes, LDS tree and second launch reassociate; one output element)
+int zkt_hostcheck_fp_vec(int field, int op, const uint32_t* a, const uint32_t* b, int e_words, int shared, uint32_t* o, size_t n) {
+  auto run = [&](auto tag) {
+    typedef decltype(tag) C; constexpr int A = C::ABI_N;
+    if (op == 2) { Fp<C> acc = fp_zero<C>(); for (size_t i = 0; i < n; ++i) acc = fp_add(acc, ld_fp<C>(a + i * A)); st_fp<C>(o, acc); return; }
+    for (size_t i = 0; i < n; ++i) {
+      if (op == 0) st_fp<C>(o + i * A, fp_pow(ld_fp<C>(a + i * A), b + (shared ? 0 : i * (size_t)e_words), e_words));
+      else st_fp<C>(o + i * A, fp_mul(ld_fp<C>(a + i * A), ld_fp<C>(b)));
+    }
+  };
+  switch (field) { case 0: run(FqC{}); break; case 1: run(FrC{}); break; case 2: run(SpC{}); break; default: run(SnC{}); }
+  return 0;
+}
+// k_tower_op (zkt_field.hip) on a batch, zero test included: op 0 add 1 sub 2 mul 3 inv 4 neg 5 reduce (mul_xi / mul_v; not for Fq12).
+// Returns the lowest index whose inverse was asked of zero, or -1.
+long zkt_hostcheck_tower_batch(int deg, int op, const uint32_t* a, const uint32_t* b, uint32_t* o, size_t n) {
+  long first = -1;
+  for (size_t i = 0; i < n; ++i) {
+    const size_t w = (size_t)deg * 12 * i;
+    bool zero = false;
+    if (deg == 2) zero = op == 3 && fq2_is_zero(ld_fq2(a + w));
+    else if (deg == 6) zero = op == 3 && fq6_is_zero(ld_fq6(a + w));
+    else { const Fq12 x = ld_fq12(a + w); zero = op == 3 && fq6_is_zero(x.c0) && fq6_is_zero(x.c1); }
+    if (zero) { if (first < 0) first = (long)i; for (int j = 0; j < deg * 12; ++j) o[w + j] = a[w + j]; continue; }
+    if (deg == 12 && op == 5) return -2;
+    zkt_hostcheck_tower(deg, op, a + w, b ? b + w : a + w, o + w);
+  }
+  return first;
+}
+// k_fq12_pow: every element to one run-time exponent of nl 32-bit words
+int zkt_hostcheck_fq12_pow(const uint32_t* a, const uint32_t* e, int nl, uint32_t* o, size_t n) {
+  for (size_t i = 0; i < n; ++i) st_fq12(o + i * 144, fq12_pow(ld_fq12(a + i * 144), e, nl));
+  return 0;
+}
+}  // extern "C"
+// the curve constants of zkt_group.hip (CurveB lives in that kernel file, so it is repeated here): y^2 = x^3 + 4, x^3 + 4(1+u), x^3 + 7
+template <class F> struct HostCurveB;
+template <> struct HostCurveB<FqOps> { static Fq b() { uint32_t w[12] = {4}; return fp_from_words<FqC>(w); } };
+template <> struct HostCurveB<Fq2Ops> { static Fq2 b() { const Fq f = HostCurveB<FqOps>::b(); return Fq2{f, f}; } };
+template <> struct HostCurveB<SpOps> { static SpE b() { uint32_t w[8] = {7}; return fp_from_words<SpC>(w); } };
+template <class F> static void pt_batch(int op, const uint32_t* a, const uint32_t* b, int kw, int k_stride, uint32_t* o, size_t n) {
+  constexpr int W = PtIO<F>::WORDS;
+  for (size_t i = 0; i < n; ++i) {
+    Aff<F> p = PtIO<F>::ld(a + i * W);
+    if (op == 0) PtIO<F>::st(o + i * W, jac_to_aff(jac_add_aff(jac_from_aff(p), PtIO<F>::ld(b + i * W))));                 // k_group_add
+    else if (op == 2) PtIO<F>::st(o + i * W, jac_to_aff(scalar_mul_aff<F>(p, b + i * (size_t)k_stride, kw)));              // k_group_mul, 2..12 words
+    else if (op == 3) { if (!p.inf) p.y = F::neg(p.y); PtIO<F>::st(o + i * W, p); }                                        // k_group_neg
+    else if (op == 7) o[i] = !p.inf && F::eq(F::sqr(p.y), F::add(F::mul(F::sqr(p.x), p.x), HostCurveB<F>::b()));               // k_group_pred<F, 0>
+    else { uint32_t k[SCALAR_MAX_LIMBS]; for (int j = 0; j < kw; ++j) k[j] = b[j]; o[i] = p.inf || jac_is_inf(scalar_mul_aff<F>(p, k, kw)); }   // k_group_pred<F, 1>: b = the order
+  }
+}
+// the sum kernels' shape (k_group_sum_partials / k_group_sum_finish): `lanes` strided mixed-addition accumulators folded pairwise by jac_add from the top half down
+template <class F> static void pt_sum(const uint32_t* a, size_t n, int lanes, uint32_t* o) {
+  constexpr int W = PtIO<F>::WORDS;
+  std::vector<Jac<F>> acc((size_t)lanes, jac_inf<F>());
+  for (size_t i = 0; i < n; ++i) acc[i % lanes] = jac_add_aff(acc[i % lanes], PtIO<F>::ld(a + i * W));
+  for (int d = lanes / 2; d >= 1; d >>= 1) for (int l = 0; l < d; ++l) acc[l] = jac_add(acc[l], acc[l + d]);
+  PtIO<F>::st(o, jac_to_aff(acc[0]));
+}
+// the generator's comb table and its digit walk (k_generator_table / k_generator_mul, zkt_group.hip): table[w * 15 + d - 1] = d * 16^w * G, a product is at most 64 mixed additions
+template <class F> static void pt_comb(const uint32_t* gen_abi, const uint32_t* scalars, uint32_t* o, size_t n) {
+  constexpr int W = PtIO<F>::WORDS;
+  static std::vector<Aff<F>> table;
+  if (table.empty()) for (int t = 0; t < 64 * 15; ++t) {
+    const int w = t / 15; const uint32_t d = (uint32_t)(t % 15) + 1u;
+    uint32_t k[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    k[w >> 3] = d << ((w & 7) * 4);
+    table.push_back(jac_to_aff(scalar_mul_aff<F>(PtIO<F>::ld(gen_abi), k, 8)));
+  }
+  for (size_t i = 0; i < n; ++i) {
+    Jac<F> acc = jac_inf<F>();
+    for (int w = 0; w < 64; ++w) {
+      const uint32_t d = (scalars[i * 8 + (w >> 3)] >> ((w & 7) * 4)) & 15u;
+      if (d) { Aff<F> q = table[(size_t)w * 15 + d - 1]; q.inf = false; acc = jac_add_aff(acc, q); }
+    }
+    PtIO<F>::st(o + i * W, jac_to_aff(acc));
+  }
+}
+extern "C" {
+// grp: 0 G1, 1 G2, 2 secp256k1.  op: 0 add, 2 scalar mul (b: kw 32-bit words per scalar, k_stride 0 = one scalar for every point), 3 neg, 4 order * P == infinity (b = order, kw words; o: one word per point), 7 on the curve and not at infinity (o: one word per point),
+// 5 sum of the n points with `kw` lanes (o: one point), 6 generator products through the comb table (a = the generator, b = n scalars of 8 words; G1 and G2)
+int zkt_hostcheck_group_batch(int grp, int op, const uint32_t* a, const uint32_t* b, int kw, int k_stride, uint32_t* o, size_t n) {
+  if (op == 5) { if (kw < 1 || (kw & (kw - 1))) return -1; if (grp == 0) pt_sum<FqOps>(a, n, kw, o); else if (grp == 1) pt_sum<Fq2Ops>(a, n, kw, o); else pt_sum<SpOps>(a, n, kw, o); return 0; }
+  if (op == 6) { if (grp == 0) pt_comb<FqOps>(a, b, o, n); else if (grp == 1) pt_comb<Fq2Ops>(a, b, o, n); else return -1; return 0; }
+  if (kw > SCALAR_MAX_LIMBS) return -1;
+  if (grp == 0) pt_batch<FqOps>(op, a, b, kw, k_stride, o, n); else if (grp == 1) pt_batch<Fq2Ops>(op, a, b, kw, k_stride, o, n); else pt_batch<SpOps>(op, a, b, kw, k_stride, o, n);
+  return 0;
+}
+}  // extern "C"
