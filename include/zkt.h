@@ -356,6 +356,26 @@ int zkt_g1_msm_dev(const zkt_g1_bases* bases, const uint64_t* dev_scalars, size_
 #define ZKT_SECP_PARTIAL_WORDS 24
 int zkt_g1_msm_submit(zkt_g1_bases* bases, const uint64_t* dev_scalars, size_t n, void* stream, int slot);
 int zkt_g1_msm_collect(zkt_g1_bases* bases, int slot, zkt_g1_affine* out, uint32_t* dev_partial_jac);
+/* Batched form: k scalar vectors over ONE resident base set in one pass.  The reference evaluates several scalar vectors over the same
+ * points one after the other: eval_with_g1_hidings / eval_with_g2_hidings (polynomial.rs:271-293) are called in loops over one CRS, and the
+ * range proof (bulletproofs.rs:58-147) takes five (AffinePoints * PrimeFieldElems).sum() over the same generators.  Below 2^19 terms every
+ * kernel of an MSM is a latency-bound sliver of the chip, and k MSMs on k slots are k such chains side by side; the batch runs one chain
+ * whose grids cover all k vectors.  Vector v is the n 4-limb scalars at dev_scalars + v * vec_stride * 4 (vec_stride counts scalars,
+ * vec_stride >= n; scalars are used as-is).  out: k host points, out[v] bit-identical to zkt_*_msm_dev of vector v alone; dev_partials_jac:
+ * k * ZKT_*_PARTIAL_WORDS u32 on the device, each in the layout of the single-MSM partial (zkt_*_jac_sum_dev and the sharded combine accept
+ * each of them).  Either may be NULL in collect; _dev needs at least one, like zkt_*_msm_dev.  submit() orders the batch behind `stream` and
+ * returns at once, collect() blocks until its results are available; _dev is both under one hold of the handle's lock.  One batch may be in
+ * flight per handle; it has a workspace and a completion event of its own, so slot MSMs and a batch may be in flight on one handle together.
+ * The workspace is allocated on the first batch and grown when a later batch has a larger k; after that a batch allocates nothing.
+ * ZKT_ERR_SHAPE: a null handle, n != zkt_*_bases_len, k == 0 or k > ZKT_MSM_BATCH_MAX, k * n > ZKT_MSM_BATCH_MAX_TERMS, vec_stride < n, a
+ * submit while a batch is in flight, a collect with none in flight — and n >= 2^19: there the accumulate of ONE MSM fills the chip and the
+ * slot ring already overlaps the stages, so use zkt_*_msm_submit.  n == 0 is valid and gives k points at infinity. */
+#define ZKT_MSM_BATCH_MAX 32                          /* vectors per batch */
+#define ZKT_MSM_BATCH_MAX_TERMS ((size_t)1 << 22)     /* k * n of one batch */
+int zkt_g1_msm_batch_submit(zkt_g1_bases* bases, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream);
+int zkt_g1_msm_batch_collect(zkt_g1_bases* bases, zkt_g1_affine* out, uint32_t* dev_partials_jac);
+int zkt_g1_msm_batch_dev(zkt_g1_bases* bases, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream,
+                         zkt_g1_affine* out, uint32_t* dev_partials_jac);
 /* combine step of a sharded MSM: sum `count` Jacobian partials (ZKT_G1_PARTIAL_WORDS u32 words each, device)
  * and normalise to affine on the host */
 int zkt_g1_jac_sum_dev(const uint32_t* dev_partials, size_t count, void* stream, zkt_g1_affine* out);
@@ -372,6 +392,10 @@ void zkt_g2_bases_free(zkt_g2_bases* b);
 int zkt_g2_msm_dev(const zkt_g2_bases* bases, const uint64_t* dev_scalars, size_t n, void* stream, zkt_g2_affine* out, uint32_t* dev_partial_jac);
 int zkt_g2_msm_submit(zkt_g2_bases* bases, const uint64_t* dev_scalars, size_t n, void* stream, int slot);
 int zkt_g2_msm_collect(zkt_g2_bases* bases, int slot, zkt_g2_affine* out, uint32_t* dev_partial_jac);
+int zkt_g2_msm_batch_submit(zkt_g2_bases* bases, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream);
+int zkt_g2_msm_batch_collect(zkt_g2_bases* bases, zkt_g2_affine* out, uint32_t* dev_partials_jac);
+int zkt_g2_msm_batch_dev(zkt_g2_bases* bases, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream,
+                         zkt_g2_affine* out, uint32_t* dev_partials_jac);
 int zkt_g2_jac_sum_dev(const uint32_t* dev_partials, size_t count, void* stream, zkt_g2_affine* out);
 int zkt_secp_bases_upload(const zkt_secp_affine* host_bases, size_t n, zkt_secp_bases** out);
 int zkt_secp_bases_from_device(const zkt_secp_affine* dev_bases, size_t n, void* stream, zkt_secp_bases** out);
@@ -380,6 +404,10 @@ void zkt_secp_bases_free(zkt_secp_bases* b);
 int zkt_secp_msm_dev(const zkt_secp_bases* bases, const uint64_t* dev_scalars, size_t n, void* stream, zkt_secp_affine* out, uint32_t* dev_partial_jac);
 int zkt_secp_msm_submit(zkt_secp_bases* bases, const uint64_t* dev_scalars, size_t n, void* stream, int slot);
 int zkt_secp_msm_collect(zkt_secp_bases* bases, int slot, zkt_secp_affine* out, uint32_t* dev_partial_jac);
+int zkt_secp_msm_batch_submit(zkt_secp_bases* bases, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream);
+int zkt_secp_msm_batch_collect(zkt_secp_bases* bases, zkt_secp_affine* out, uint32_t* dev_partials_jac);
+int zkt_secp_msm_batch_dev(zkt_secp_bases* bases, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream,
+                           zkt_secp_affine* out, uint32_t* dev_partials_jac);
 int zkt_secp_jac_sum_dev(const uint32_t* dev_partials, size_t count, void* stream, zkt_secp_affine* out);
 
 /* f-3: Groth16 at scale on the reference's evaluation domain {1..n}.  The reference keeps (m+1) dense interpolated

@@ -1,0 +1,104 @@
+"""The batched MSM's plan and bucket layout (zk-toolkit_amd/csrc/zkt_msm.hip, msm_plan_batch / k_digits_batch) restated in numpy, on top of
+tests/msm_plan_model.py, plus the constructed scalar vectors of tests/test_gpu_msm_batch.py.
+
+TEST INFRASTRUCTURE, like msm_plan_model.py: it says which buckets a batch of scalar vectors fills, so that a GPU case can claim "vector v ends in the last
+bucket of its set and vector v + 1 starts in the first bucket of the next" and have the claim checked on the CPU (tests/test_msm_batch_model.py)."""
+import numpy as np
+import msm_plan_model as M
+
+# ---- limits, each restating one line of include/zkt.h or zkt_api.cpp ----------------------------------------------------------------
+BATCH_MAX = 32                       # include/zkt.h, `#define ZKT_MSM_BATCH_MAX 32`
+BATCH_MAX_TERMS = 1 << 22            # include/zkt.h, `#define ZKT_MSM_BATCH_MAX_TERMS ((size_t)1 << 22)`: k * n of one batch
+BATCH_MAX_N = 1 << 19                # zkt_api.cpp, msm_batch_submit_locked `n >= (size_t(1) << 19)` is refused: one MSM fills the chip there
+GROUPS = M.GROUPS
+FUNCTIONS = tuple(f"zkt_{g}_msm_batch_{f}" for g in GROUPS for f in ("submit", "collect", "dev"))
+
+# n on both sides of every width step of msm_plan below the graph limit (the batch keeps the handle's width); the batch plan has no sort threshold of
+# its own: k_digits_batch sorts at every size
+WIDTH_STEPS = (1, 1023, 1024, 2047, 2048, 16383, 16384)
+BATCH_SIZES = (1, 2, 5)
+BOUNDARY_N = (1023, 1024, 2048, 16384)          # one n for every window width in WIDTH_STEPS: c = 10, 11, 13, 16
+
+
+def accepts(n, k, vec_stride, bases_len):
+    """the ZKT_ERR_SHAPE rules of zkt_*_msm_batch_submit that depend on the numbers alone"""
+    return n == bases_len and 1 <= k <= BATCH_MAX and k * n <= BATCH_MAX_TERMS and vec_stride >= n and n < BATCH_MAX_N
+
+
+def plan(n, group, k):
+    """dict(c, nwin, half, nbuckets, chunk) of msm_plan_batch: the width of the resident plan (the handle's table was built for it), k bucket sets of
+    2^(c-1) buckets, the task size picked over all k * nwin * n digits"""
+    p = M.plan(n, group, "resident")
+    return dict(c=p["c"], nwin=p["nwin"], half=p["half"], nbuckets=k * p["half"], chunk=M.pick_chunk(k * p["nwin"] * n, group), k=k)
+
+
+def bucket_ids(vectors, inf, c, nwin):
+    """bucket of every (vector, window, term) as a (k, nwin, n) array, -1 where k_digits_batch writes no entry: v * half + |digit| - 1"""
+    half = 1 << (c - 1)
+    out = []
+    for v, s in enumerate(vectors):
+        b = M.bucket_ids(s, inf, c, nwin, "resident")
+        out.append(np.where(b >= 0, b + v * half, -1))
+    return np.stack(out)
+
+
+def entry_ids(n, nwin):
+    """the entry k_digits_batch files for (window w, term i), whatever the vector: the index w * n + i into the ONE resident window-multiple table"""
+    return np.arange(nwin, dtype=np.int64)[:, None] * n + np.arange(n, dtype=np.int64)[None, :]
+
+
+def census(vectors, n, group):
+    p = plan(n, group, len(vectors))
+    b = bucket_ids(vectors, None, p["c"], p["nwin"])
+    flat = b[b >= 0]
+    count = np.bincount(flat, minlength=p["nbuckets"]).astype(np.int64)
+    ch = p["chunk"]
+    nt = np.where(count <= ch, 1, (count + ch - 1) // ch)
+    return dict(plan=p, buckets=b, count=count, nt=nt, hot=int((nt > M.HOT_NT).sum()))
+
+
+# ---- constructed vectors ----------------------------------------------------------------------------------------------------------
+def full_windows(c):
+    return 256 // c                  # windows whose c bits all lie below bit 256
+
+
+def last_bucket_scalar(c):
+    """every full window holds the digit 2^(c-1): positive (raw > half is the negative case), no carry — the LAST bucket of the vector's set"""
+    return sum((1 << (c - 1)) << (c * w) for w in range(full_windows(c)))
+
+
+def first_bucket_scalar(c):
+    """every full window holds the digit 1: the FIRST bucket of the vector's set"""
+    return sum(1 << (c * w) for w in range(full_windows(c)))
+
+
+def boundary_vectors(n, group, swapped):
+    """two vectors of n equal scalars: (last-bucket, first-bucket), or the other way round"""
+    c = M.plan(n, group, "resident")["c"]
+    a = M.scalars_from_ints([last_bucket_scalar(c)] * n)
+    b = M.scalars_from_ints([first_bucket_scalar(c)] * n)
+    return [b, a] if swapped else [a, b]
+
+
+MIXED_N, MIXED_STRIDE_PAD = 16384, 3
+
+
+def mixed_vectors(group):
+    """the five vectors of the mixed case: random | all zero | 0/1 | one value in every term | order - 1 and 2^256 - 1 alternating"""
+    n, order = MIXED_N, M.ORDER[group]
+    rnd = M.random_scalars(71, n, order)
+    zero = np.zeros((n, 4), np.uint64)
+    bits = np.zeros((n, 4), np.uint64)
+    bits[:, 0] = np.random.Generator(np.random.PCG64(72)).integers(0, 2, size=n, dtype=np.uint64)
+    same = np.tile(M.random_scalars(73, 1, order), (n, 1))
+    edge = M.scalars_from_ints([order - 1 if i % 2 == 0 else (1 << 256) - 1 for i in range(n)])
+    return [rnd, zero, bits, same, edge]
+
+
+POOL_N = 16384                       # the largest n of WIDTH_STEPS: every random vector is a prefix of one pool per (group, vector)
+
+
+def random_vectors(group, n, k, seed=80):
+    """k distinct uniform vectors of n <= POOL_N scalars (prefixes of the group's pools)"""
+    assert n <= POOL_N
+    return [M.random_scalars(seed + v, POOL_N, M.ORDER[group])[:n] for v in range(k)]

@@ -68,6 +68,9 @@ def lib():
         for grp in ("g1", "g2", "secp"):
             getattr(L, f"zkt_{grp}_msm_submit").argtypes = [vp, vp, sz, vp, ctypes.c_int]
             getattr(L, f"zkt_{grp}_msm_collect").argtypes = [vp, ctypes.c_int, vp, vp]
+            getattr(L, f"zkt_{grp}_msm_batch_submit").argtypes = [vp, vp, sz, sz, sz, vp]
+            getattr(L, f"zkt_{grp}_msm_batch_collect").argtypes = [vp, vp, vp]
+            getattr(L, f"zkt_{grp}_msm_batch_dev").argtypes = [vp, vp, sz, sz, sz, vp, vp, vp]
         for f in ("fq", "fr", "sp", "sn"):
             getattr(L, f"zkt_{f}_pow_batch").argtypes = [vp, vp, sz, ctypes.c_int, vp, sz]
             getattr(L, f"zkt_{f}_pow_seq").argtypes = [vp, sz, vp]

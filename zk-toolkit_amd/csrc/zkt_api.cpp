@@ -161,6 +161,15 @@ struct MsmSlot {                      // one in-flight MSM: workspace, result bu
   static constexpr int NGRAPH = 4;
   hipGraphExec_t gexec[NGRAPH] = {}; const void* gkey[NGRAPH] = {}; unsigned gnext = 0; bool timed = false;
 };
+struct MsmBatch {                     // the one in-flight batch of a handle (zkt_*_msm_batch_*): independent of the slots, created on the first batch
+  hipEvent_t e_in = nullptr, e_done = nullptr;
+  void* workspace = nullptr;          // msm_plan_batch(n, grp, cap).ws_bytes: grown when a later batch has more vectors
+  uint32_t* d_jac = nullptr;          // cap Jacobian partials, 3 coordinates each
+  uint32_t* d_abi = nullptr;          // cap ABI points
+  uint8_t* h_out = nullptr;           // pinned, cap ABI points
+  int cap = 0, k = 0;                 // vectors the buffers hold / vectors of the batch in flight
+  bool busy = false;
+};
 struct zkt_bases_impl {               // one resident base set of any group; zkt_g1_bases / zkt_g2_bases / zkt_secp_bases are this
   size_t n = 0;
   int grp = G_G1;
@@ -178,6 +187,7 @@ struct zkt_bases_impl {               // one resident base set of any group; zkt
   // (measured: the A sum of a proof started 16 ms late behind the C1 reduce, profiles/r03_groth16_timeline.txt)
   bool own_streams = true, acc_owned = false, grouped = false; int tail_base = 0, tail_span = 0;
   MsmSlot slot[MSM_SLOTS];
+  MsmBatch batch;
   std::mutex mu;                 // slot state: calls on one handle are serialised (submit/collect of different slots may come from different threads)
 };
 struct zkt_g1_bases : zkt_bases_impl {};
@@ -511,8 +521,14 @@ static int bases_build(zkt_bases_impl* h, const uint32_t* dev_abi, hipStream_t s
   HIPCHK(e);
   return ZKT_OK;
 }
+static void batch_release(MsmBatch& Bt) {
+  if (Bt.workspace) hipFree(Bt.workspace); if (Bt.d_jac) hipFree(Bt.d_jac); if (Bt.d_abi) hipFree(Bt.d_abi);
+  if (Bt.h_out) hipHostFree(Bt.h_out);
+  Bt.workspace = nullptr; Bt.d_jac = Bt.d_abi = nullptr; Bt.h_out = nullptr; Bt.cap = 0;
+}
 static void bases_free(zkt_bases_impl* h) {
   if (!h) return;
+  if (h->batch.busy && h->batch.e_done) hipEventSynchronize(h->batch.e_done);      // a batch in flight reads the table
   if (h->table) hipFree(h->table);
   if (h->inf) hipFree(h->inf);
   if (h->own_streams) {
@@ -529,6 +545,8 @@ static void bases_free(zkt_bases_impl* h) {
     if (S.workspace) hipFree(S.workspace); if (S.d_result_jac) hipFree(S.d_result_jac); if (S.d_out_abi) hipFree(S.d_out_abi);
     if (S.h_out) hipHostFree(S.h_out);
   }
+  for (hipEvent_t ev : {h->batch.e_in, h->batch.e_done}) if (ev) hipEventDestroy(ev);
+  batch_release(h->batch);
   delete h;
 }
 static int bases_from_device(int grp, const void* dev_bases, size_t n, void* stream, zkt_bases_impl** out) {
@@ -650,6 +668,82 @@ static int msm_dev(zkt_bases_impl* h, const uint64_t* dev_scalars, size_t n, voi
   if (rc) return rc;
   return msm_collect_locked(h, 0, out, dev_partial_jac);
 }
+// ---- batched form: k scalar vectors over the handle's base set in ONE pipeline (msm_plan_batch) -------------------------------------------------
+// Below 2^19 terms every kernel of an MSM is a latency-bound sliver of the chip, and k MSMs on k slots are k chains of ~20 such kernels side by side.  The batch
+// runs ONE chain whose grids cover all k vectors: bucket set v for vector v, one task list, one accumulate launch, the reduce kernels with grid.y = k.
+// It has a workspace, result buffers and a completion event of its own, so slot MSMs and a batch may be in flight on one handle together; it runs on the reduce
+// stream of the last slot (a grouped handle: the group's stream for that slot), issued launch by launch — no graph (profiles/msm_batch_go_no_go.md).
+static hipStream_t batch_stream(zkt_bases_impl* h) { return slot_tail_stream(h, MSM_SLOTS - 1); }
+static int batch_ready(zkt_bases_impl* h, int k) {      // buffers for k vectors: allocates on the first batch and when k exceeds every earlier one
+  int rc = streams_ready(h); if (rc) return rc;
+  MsmBatch& Bt = h->batch;
+  if (!Bt.e_in) HIPCHK(hipEventCreateWithFlags(&Bt.e_in, hipEventDisableTiming));
+  if (!Bt.e_done) HIPCHK(hipEventCreateWithFlags(&Bt.e_done, hipEventDisableTiming));
+  if (k <= Bt.cap) return ZKT_OK;
+  HIPCHK(hipStreamSynchronize(batch_stream(h)));         // nothing of an earlier (collected) batch is still queued on the buffers about to go
+  batch_release(Bt);
+  const size_t wsb = msm_plan_batch(h->n, h->grp, k).ws_bytes, ptb = abi_pt_bytes(h->grp);
+  HIPCHK(hipMalloc(&Bt.workspace, wsb));
+  if (debug_poison()) { HIPCHK(hipMemset(Bt.workspace, 0xA5, wsb)); HIPCHK(hipDeviceSynchronize()); }
+  HIPCHK(hipMalloc((void**)&Bt.d_jac, (size_t)k * 3 * grp_coord_bytes(h->grp)));
+  HIPCHK(hipMalloc((void**)&Bt.d_abi, (size_t)k * ptb));
+  HIPCHK(hipHostMalloc((void**)&Bt.h_out, (size_t)k * ptb, hipHostMallocDefault));
+  Bt.cap = k;
+  return ZKT_OK;
+}
+// caller holds h->mu
+static int msm_batch_submit_locked(zkt_bases_impl* h, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream) {
+  if (n != h->n || k == 0 || k > ZKT_MSM_BATCH_MAX || vec_stride < n || n >= (size_t(1) << 19) || k * n > ZKT_MSM_BATCH_MAX_TERMS || (n && !dev_scalars)) return ZKT_ERR_SHAPE;
+  if (h->batch.busy) return ZKT_ERR_SHAPE;               // collect it first
+  const MsmPlan P = msm_plan_batch(n, h->grp, (int)k);
+  if (P.c != h->plan.c || P.nwin != h->plan.nwin || P.nbuckets > (size_t(1) << 21)) return ZKT_ERR_SHAPE;      // the entries index the table the handle was built with
+  int rc = batch_ready(h, (int)k); if (rc) return rc;
+  MsmBatch& Bt = h->batch;
+  hipStream_t st = batch_stream(h);
+  HIPCHK(hipEventRecord(Bt.e_in, (hipStream_t)stream));   // the scalars are produced on the caller's stream
+  HIPCHK(hipStreamWaitEvent(st, Bt.e_in, 0));
+  HIPCHK(launch_msm_sort_batch(P, h->inf, (const uint32_t*)dev_scalars, vec_stride, Bt.workspace, st));
+  HIPCHK(launch_msm_accumulate(P, h->table, Bt.workspace, st));
+  HIPCHK(launch_msm_reduce(P, Bt.workspace, Bt.d_jac, Bt.d_abi, st));
+  HIPCHK(hipMemcpyAsync(Bt.h_out, Bt.d_abi, k * abi_pt_bytes(h->grp), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(Bt.e_done, st));
+  Bt.k = (int)k; Bt.busy = true;
+  return ZKT_OK;
+}
+static int msm_batch_collect_locked(zkt_bases_impl* h, void* out, uint32_t* dev_partials_jac) {
+  MsmBatch& Bt = h->batch;
+  if (!Bt.busy) return ZKT_ERR_SHAPE;
+  HIPCHK(hipEventSynchronize(Bt.e_done));
+  if (dev_partials_jac) {       // copied on the batch's own stream and waited for: complete when this returns, never overtaken by the next batch
+    hipStream_t st = batch_stream(h);
+    HIPCHK(hipMemcpyAsync(dev_partials_jac, Bt.d_jac, (size_t)Bt.k * 3 * grp_coord_bytes(h->grp), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  if (out) memcpy(out, Bt.h_out, (size_t)Bt.k * abi_pt_bytes(h->grp));
+  t_kernel_ms = 0.f; t_kernel_name = "msm_batch";
+  Bt.busy = false;
+  return ZKT_OK;
+}
+static int msm_batch_submit(zkt_bases_impl* h, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!h) return ZKT_ERR_SHAPE;
+  std::lock_guard<std::mutex> lk(h->mu);
+  return msm_batch_submit_locked(h, dev_scalars, n, k, vec_stride, stream);
+}
+static int msm_batch_collect(zkt_bases_impl* h, void* out, uint32_t* dev_partials_jac) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!h) return ZKT_ERR_SHAPE;
+  std::lock_guard<std::mutex> lk(h->mu);
+  return msm_batch_collect_locked(h, out, dev_partials_jac);
+}
+static int msm_batch_dev(zkt_bases_impl* h, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream, void* out, uint32_t* dev_partials_jac) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!h || (!out && !dev_partials_jac)) return ZKT_ERR_SHAPE;
+  std::lock_guard<std::mutex> lk(h->mu);
+  int rc = msm_batch_submit_locked(h, dev_scalars, n, k, vec_stride, stream);
+  if (rc) return rc;
+  return msm_batch_collect_locked(h, out, dev_partials_jac);
+}
 // `dst` works on `src`'s streams from now on (sort stream and reduce streams [tail_base, tail_base + tail_span); the accumulate stream too if share_acc,
 // otherwise dst gets one of its own).  Call before dst's first MSM; free dst before src.
 int zkt_internal_bases_share_streams(void* dst_, void* src_, int share_acc, int tail_base, int tail_span) {
@@ -728,6 +822,10 @@ static int msm_host(int grp, const void* bases, const uint64_t* scalars, size_t 
   int zkt_##NAME##_msm_collect(zkt_##NAME##_bases* b, int slot, PT* out, uint32_t* partial) { return msm_collect(b, slot, out, partial); } \
   int zkt_##NAME##_msm_dev(const zkt_##NAME##_bases* b, const uint64_t* k, size_t n, void* stream, PT* out, uint32_t* partial) { \
     return msm_dev(const_cast<zkt_##NAME##_bases*>(b), k, n, stream, out, partial); }                                              \
+  int zkt_##NAME##_msm_batch_submit(zkt_##NAME##_bases* b, const uint64_t* k, size_t n, size_t nv, size_t vs, void* stream) { return msm_batch_submit(b, k, n, nv, vs, stream); } \
+  int zkt_##NAME##_msm_batch_collect(zkt_##NAME##_bases* b, PT* out, uint32_t* partials) { return msm_batch_collect(b, out, partials); } \
+  int zkt_##NAME##_msm_batch_dev(zkt_##NAME##_bases* b, const uint64_t* k, size_t n, size_t nv, size_t vs, void* stream, PT* out, uint32_t* partials) { \
+    return msm_batch_dev(b, k, n, nv, vs, stream, out, partials); }                                                                 \
   int zkt_##NAME##_jac_sum_dev(const uint32_t* partials, size_t count, void* stream, PT* out) { return jac_sum_dev(GRP, partials, count, stream, out); } \
   int zkt_##NAME##_msm(const PT* bases, const uint64_t* scalars, size_t n, PT* out) { return msm_host(GRP, bases, scalars, n, out); }
 ZKT_BASES_API(g1, G_G1, zkt_g1_affine)

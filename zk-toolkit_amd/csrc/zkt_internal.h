@@ -130,6 +130,7 @@ struct MsmPlan {
   int direct;          // 1 = table-free one-shot form: `table` is the n bases themselves, every window has its own 2^(c-1) buckets
   size_t half;         // buckets per window, 2^(c-1)
   uint32_t chunk;      // most entries one accumulate task (lane) adds: buckets with more are cut into equal pieces (8..128, pick_chunk)
+  int batch = 0;       // batched form: scalar vectors that share the resident table; vector v owns buckets [v * half, (v+1) * half), nbuckets = batch * half
 };
 MsmPlan msm_plan(size_t n, int grp);
 // table-free form for one-shot calls (zkt_*_msm with host pointers): no window-multiple table to build — nwin bucket sets, the per-window
@@ -142,6 +143,11 @@ hipError_t launch_msm_to_kernel_layout(int grp, const uint32_t* abi_pts, uint32_
 // tmp: (nwin - 1) * n * 2 coordinates of scratch (same layout as the table rows 1..nwin-1), only needed during the call
 hipError_t launch_msm_precompute(int grp, uint32_t* table, uint8_t* inf, size_t n, int c, int nwin, uint32_t* tmp, hipStream_t s);
 hipError_t launch_msm_sort(const MsmPlan& plan, const uint8_t* base_inf, const uint32_t* scalars, void* workspace, hipStream_t s);
+// batched form (zkt_*_msm_batch_*): k <= 32 scalar vectors over one resident base set in one pass — the window width of msm_plan(n, grp), k bucket sets, one
+// task list; launch_msm_sort_batch files vector v (its scalars at scalars + v * vec_stride * 8) into set v, launch_msm_accumulate runs as for one MSM, and
+// launch_msm_reduce writes k Jacobian partials (3 coordinates each, contiguous) and k affine ABI points
+MsmPlan msm_plan_batch(size_t n, int grp, int k);
+hipError_t launch_msm_sort_batch(const MsmPlan& plan, const uint8_t* base_inf, const uint32_t* scalars, size_t vec_stride, void* workspace, hipStream_t s);
 hipError_t launch_msm_accumulate(const MsmPlan& plan, const uint32_t* table, void* workspace, hipStream_t s);
 hipError_t launch_msm_reduce(const MsmPlan& plan, void* workspace, uint32_t* dev_result_jac, uint32_t* dev_out_abi, hipStream_t s);
 // out = a + b on two Jacobian partials (3 coordinates each)

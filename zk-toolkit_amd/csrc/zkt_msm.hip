@@ -277,6 +277,58 @@ static __global__ void __launch_bounds__(256) k_digits(const uint32_t* __restric
   }
 }
 
+// Batched form (msm_plan_batch): grid.y = scalar vector.  Vector v reads its scalars `vec_stride` scalars after vector v-1's and files its digits into bucket set v,
+// buckets [v * 2^(c-1), (v+1) * 2^(c-1)); the entries still index the ONE resident window-multiple table (w * n + i, sign in bit 31), so the k bucket sets are
+// accumulated by the same gather as one.  Slots are kept per (vector, window).  Zero digits, points at infinity and the wave-level aggregation are k_digits'.
+template <bool SCATTER>
+static __global__ void __launch_bounds__(256) k_digits_batch(const uint32_t* __restrict__ scalars, size_t vec_stride, const uint8_t* __restrict__ inf, size_t n, int c, int nwin,
+                                                      uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets,
+                                                      uint32_t* __restrict__ slot, uint32_t* __restrict__ entries) {
+  ZKT_SIDE_PRIO;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, v = blockIdx.y;
+  const bool live = i < n;
+  uint32_t k[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (live) {
+    const uint4* sp = reinterpret_cast<const uint4*>(scalars + (v * vec_stride + i) * 8);
+    uint4 lo = sp[0], hi = sp[1];
+    k[0] = lo.x; k[1] = lo.y; k[2] = lo.z; k[3] = lo.w; k[4] = hi.x; k[5] = hi.y; k[6] = hi.z; k[7] = hi.w;
+  }
+  const uint32_t half = 1u << (c - 1), set = (uint32_t)v * half;
+  slot += v * (size_t)nwin * n;
+  const unsigned lane = threadIdx.x & 63;
+  const unsigned long long lt_mask = (1ull << lane) - 1ull;
+  uint32_t carry = 0;
+  for (int w = 0; w < nwin; ++w) {                      // wave-uniform trip count: the ballots below need every lane here
+    uint32_t raw = window_bits(k, w, c) + carry;
+    uint32_t neg = raw > half;
+    uint32_t mag = neg ? (1u << c) - raw : raw;         // |digit| in [0, 2^(c-1)]
+    carry = neg;
+    const size_t src = (size_t)w * n + i;
+    const uint32_t b = set + mag - 1;
+    if (SCATTER) {
+      if (live) { const uint32_t pos = slot[src]; if (pos != NO_SLOT) entries[offsets[b] + pos] = (uint32_t)src | (neg << 31); }
+      continue;
+    }
+    bool todo = live && mag != 0 && !inf[live ? src : 0];   // infinity and zero digits contribute nothing
+    uint32_t pos = NO_SLOT;
+    for (int round = 0; round < 2; ++round) {
+      unsigned long long act = __ballot(todo);
+      if (act == 0) break;
+      int leader = __ffsll((long long)act) - 1;
+      uint32_t lb = __shfl(b, leader);
+      unsigned long long same = __ballot(todo && b == lb);
+      int cnt = __popcll(same);
+      if (cnt < 4) break;                               // nothing worth aggregating: fall through to individual atomics
+      uint32_t base = 0;
+      if ((int)lane == leader) base = atomicAdd(&counts[lb], (uint32_t)cnt);
+      base = __shfl(base, leader);
+      if (todo && b == lb) { pos = base + (uint32_t)__popcll(same & lt_mask); todo = false; }
+    }
+    if (todo) pos = atomicAdd(&counts[b], 1u);
+    if (live) slot[src] = pos;
+  }
+}
+
 // exclusive scan of counts[0..m) into offsets[0..m]: per-block sums, scan of the block sums, per-block scan.
 static constexpr int SCAN_TPB = 256, SCAN_ITEMS = 8, SCAN_TILE = SCAN_TPB * SCAN_ITEMS;
 __device__ inline uint32_t block_excl_scan_256(uint32_t v, uint32_t* lds /*256*/, uint32_t& total) {
@@ -631,15 +683,32 @@ __global__ void __launch_bounds__(64) k_join_windows(const uint32_t* __restrict_
   }
 }
 
+// batched form: the k sums k_combine left XYW words apart -> k Jacobian partials in the 3-coordinate layout of a single MSM's partial, and the k affine ABI points.
+// One lane per vector (k <= 32): the k inversions run side by side in one wave.
+template <class F>
+__global__ void __launch_bounds__(64) k_batch_finish(const uint32_t* __restrict__ sum_jac, int k, uint32_t* __restrict__ out_jac, uint32_t* __restrict__ out_abi) {
+  ZKT_SIDE_PRIO;
+  constexpr int CW = Coord<F>::CW, XYW = 4 * CW, JW = 3 * CW;
+  const int t = threadIdx.x;
+  if (t >= k) return;
+  const uint32_t* p = sum_jac + (size_t)t * XYW;
+  const Jac<F> v{Coord<F>::ld(p), Coord<F>::ld(p + CW), Coord<F>::ld(p + 2 * CW)};
+  uint32_t* o = out_jac + (size_t)t * JW;
+  Coord<F>::st(o, v.X); Coord<F>::st(o + CW, v.Y); Coord<F>::st(o + 2 * CW, v.Z);
+  PtIO<F>::st(out_abi + (size_t)t * PtIO<F>::WORDS, jac_to_aff(v));
+}
+
 namespace {
 struct MsmWs {   // workspace carve-up (one per in-flight MSM)
   uint32_t *zero_begin, *counts, *cursor, *size_hist, *size_off, *size_cur, *hot, *zero_end;   // [zero_begin, zero_end) is cleared per MSM
   uint32_t *offsets, *entries, *slot, *sums, *colsum, *rowsum, *clsA, *clsB, *win_jac, *scan_tmp, *ntask, *task_off, *partial, *hot_part;
   uint32_t *tilehist, *tileoff, *blkoff, *subhist, *part_scan; uint2* rec;   // the partition sort; rec = (entry, low bits of the bucket id) per digit
   uint2* order; size_t max_tasks;
+  uint8_t* end;                    // one past the last byte the carve hands out
 };
 MsmWs carve(const MsmPlan& P, void* workspace) {
   const size_t B = P.nbuckets, XYW = 4 * (size_t)coord_words(P.grp);
+  const size_t ent = (size_t)P.nwin * P.n * (P.batch ? (size_t)P.batch : 1);      // (vector, window, term) digits of a batch
   uint8_t* ws = (uint8_t*)workspace;
   MsmWs w;
   w.zero_begin = (uint32_t*)ws;
@@ -652,12 +721,12 @@ MsmWs carve(const MsmPlan& P, void* workspace) {
   w.zero_end = (uint32_t*)ws;
   w.offsets = (uint32_t*)ws; ws += (B + 1) * 4;
   ws = (uint8_t*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  w.entries = (uint32_t*)ws; ws += (size_t)P.nwin * P.n * 4;
+  w.entries = (uint32_t*)ws; ws += ent * 4;
   ws = (uint8_t*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  w.slot = (uint32_t*)ws; ws += (size_t)P.nwin * P.n * 4;
+  w.slot = (uint32_t*)ws; ws += ent * 4;
   ws = (uint8_t*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
   w.sums = (uint32_t*)ws; ws += B * XYW * 4;
-  const size_t nw = P.direct ? (size_t)P.nwin : 1;                // the direct form reduces every window side by side
+  const size_t nw = P.direct ? (size_t)P.nwin : P.batch ? (size_t)P.batch : 1;      // the direct form reduces every window side by side, the batched form every vector
   w.colsum = (uint32_t*)ws; ws += nw * 1024 * XYW * 4;
   w.rowsum = (uint32_t*)ws; ws += nw * 1024 * XYW * 4;
   w.clsA = (uint32_t*)ws; ws += nw * 32 * WB_SPLIT * XYW * 4;
@@ -666,12 +735,13 @@ MsmWs carve(const MsmPlan& P, void* workspace) {
   w.scan_tmp = (uint32_t*)ws; ws += 1024 * 4;
   w.ntask = (uint32_t*)ws; ws += (B + 1) * 4;
   w.task_off = (uint32_t*)ws; ws += (B + 1) * 4;
-  w.max_tasks = B + (size_t)P.nwin * P.n / P.chunk + 1;
+  w.max_tasks = B + ent / P.chunk + 1;
   ws = (uint8_t*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
   w.order = (uint2*)ws; ws += w.max_tasks * 8;
   w.partial = (uint32_t*)ws; ws += w.max_tasks * XYW * 4;
   w.hot_part = (uint32_t*)ws; ws += (size_t)HOT_CAP * HOT_FAN * XYW * 4;
-  {
+  w.rec = nullptr; w.tilehist = w.tileoff = w.blkoff = w.part_scan = w.subhist = nullptr;
+  if (!P.batch) {                                                  // the batched sort is k_digits_batch at every size: no partition scratch
     const PartDims d = part_dims(P.n, P.nbuckets, P.nwin);
     ws = (uint8_t*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
     w.rec = (uint2*)ws; ws += (((size_t)P.nwin * P.n * 8) + 255) & ~(size_t)255;
@@ -682,6 +752,7 @@ MsmWs carve(const MsmPlan& P, void* workspace) {
     ws = (uint8_t*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
     w.subhist = (uint32_t*)ws; ws += (size_t)d.maxblk * PART_SUB * 4;
   }
+  w.end = ws;
   return w;
 }
 }  // namespace
@@ -744,6 +815,26 @@ hipError_t PART(launch_msm_sort)(const MsmPlan& P, const uint8_t* inf, const uin
   hipLaunchKernelGGL(k_task_scatter, dim3(grid_blocks(B)), dim3(256), 0, s, w.counts, B, P.chunk, (const uint32_t*)w.size_hist, w.size_cur, w.order, w.hot);
   return hipGetLastError();
 }
+// the same stage for a batch (P.batch vectors, `vec_stride` scalars apart): one digit pass over (vector, term), then the task list over all P.batch bucket sets
+hipError_t PART(launch_msm_sort_batch)(const MsmPlan& P, const uint8_t* inf, const uint32_t* scalars, size_t vec_stride, void* workspace, hipStream_t s) {
+  const size_t B = P.nbuckets, n = P.n;
+  if (P.batch < 1 || P.direct || vec_stride < n || B > (size_t)1024 * SCAN_TILE) return hipErrorInvalidValue;      // (launch_scan's scratch: 1024 block sums)
+  MsmWs w = carve(P, workspace);
+  hipError_t e;
+  if ((e = zero_async(w.zero_begin, (uint8_t*)w.zero_end - (uint8_t*)w.zero_begin, s)) != hipSuccess) return e;
+  if (n) {
+    const dim3 g(grid_blocks(n), (unsigned)P.batch);
+    hipLaunchKernelGGL(k_digits_batch<false>, g, dim3(256), 0, s, scalars, vec_stride, inf, n, P.c, P.nwin, w.counts, (const uint32_t*)nullptr, w.slot, (uint32_t*)nullptr);
+    launch_scan(w.counts, w.offsets, B, w.scan_tmp, s);
+    hipLaunchKernelGGL(k_digits_batch<true>, g, dim3(256), 0, s, scalars, vec_stride, inf, n, P.c, P.nwin, (uint32_t*)nullptr, (const uint32_t*)w.offsets, w.slot, w.entries);
+  } else {
+    if ((e = zero_async(w.offsets, (B + 1) * 4, s)) != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_task_count, dim3(grid_blocks(B)), dim3(256), 0, s, w.counts, B, P.chunk, w.ntask, w.size_hist);
+  launch_scan(w.ntask, w.task_off, B, w.scan_tmp, s);
+  hipLaunchKernelGGL(k_task_scatter, dim3(grid_blocks(B)), dim3(256), 0, s, w.counts, B, P.chunk, (const uint32_t*)w.size_hist, w.size_cur, w.order, w.hot);
+  return hipGetLastError();
+}
 // stage 2 (VALU bound, the dominant kernel): one bucket per lane
 hipError_t PART(launch_msm_accumulate)(const MsmPlan& P, const uint32_t* table, void* workspace, hipStream_t s) {
   MsmWs w = carve(P, workspace);
@@ -758,7 +849,7 @@ hipError_t PART(launch_msm_accumulate)(const MsmPlan& P, const uint32_t* table, 
 }
 // stage 3 (latency bound): sum_b (b+1) S_b, b = hi*NLO + lo  ->  Jacobian partial (+ affine point if out_abi)
 hipError_t PART(launch_msm_reduce)(const MsmPlan& P, void* workspace, uint32_t* dev_result_jac, uint32_t* dev_out_abi, hipStream_t s) {
-  const size_t B = P.direct ? P.half : P.nbuckets;          // buckets of one reduction (per window in the direct form)
+  const size_t B = P.direct || P.batch ? P.half : P.nbuckets;          // buckets of one reduction (per window in the direct form, per vector in the batched form)
   MsmWs w = carve(P, workspace);
   const size_t NLO = B < 1024 ? B : 1024, NHI = B / NLO;
   int lo_bits = 0; while ((size_t(1) << lo_bits) < NLO) ++lo_bits;
@@ -769,15 +860,16 @@ hipError_t PART(launch_msm_reduce)(const MsmPlan& P, void* workspace, uint32_t* 
   int RS = 1;
   while (NHI > 1 && (size_t)(2 * RS) * NHI <= 1024 && NLO / (size_t)(2 * RS) >= 64 && NLO / (size_t)(2 * RS) >= NHI) RS *= 2;
   const size_t NROW = (size_t)RS * NHI;
-  if (P.direct) {                                          // every window reduced side by side (grid.y), then joined
-    const unsigned ny = (unsigned)P.nwin;
+  if (P.direct || P.batch) {                               // every window reduced side by side (grid.y), then joined; batched form: every vector, then finished
+    const unsigned ny = (unsigned)(P.direct ? P.nwin : P.batch);
     MSM_DISPATCH(P.grp,
       hipLaunchKernelGGL(k_merge_hot<F>, dim3(HOT_FAN, HOT_CAP), dim3(RED_TPB), 0, s, (const uint32_t*)w.task_off, (const uint32_t*)w.partial, (const uint32_t*)w.hot, w.hot_part);
       hipLaunchKernelGGL(k_merge_partials<F>, dim3((unsigned)((P.nbuckets + RED_NG - 1) / RED_NG < 4096 ? (P.nbuckets + RED_NG - 1) / RED_NG : 4096)), dim3(RED_TPB), 0, s, (const uint32_t*)w.task_off, P.nbuckets, (const uint32_t*)w.partial, (const uint32_t*)w.hot, (const uint32_t*)w.hot_part, w.sums);
       hipLaunchKernelGGL(k_marginals<F>, dim3((unsigned)(NLO + (NHI > 1 ? NROW : 0)), ny), dim3(RED_TPB), 0, s, (const uint32_t*)w.sums, NLO, NHI, RS, w.colsum, w.rowsum);
       hipLaunchKernelGGL(k_weight_bits<F>, dim3((unsigned)(nbA + nbB) * WB_SPLIT, ny), dim3(WB_TPB), 0, s, (const uint32_t*)w.colsum, NLO, nbA, (const uint32_t*)w.rowsum, NHI, RS, w.clsA, w.clsB);
       hipLaunchKernelGGL(k_combine<F>, dim3(1, ny), dim3(CMB_TPB), 0, s, (const uint32_t*)w.clsA, nbA, (const uint32_t*)w.clsB, nbB, lo_bits, w.win_jac, (uint32_t*)nullptr);
-      hipLaunchKernelGGL(k_join_windows<F>, dim3(1), dim3(64), 0, s, (const uint32_t*)w.win_jac, P.nwin, P.c, dev_result_jac, dev_out_abi));
+      if (P.direct) hipLaunchKernelGGL(k_join_windows<F>, dim3(1), dim3(64), 0, s, (const uint32_t*)w.win_jac, P.nwin, P.c, dev_result_jac, dev_out_abi);
+      else hipLaunchKernelGGL(k_batch_finish<F>, dim3(1), dim3(64), 0, s, (const uint32_t*)w.win_jac, P.batch, dev_result_jac, dev_out_abi));
     return hipGetLastError();
   }
   MSM_DISPATCH(P.grp,
@@ -840,6 +932,7 @@ hipError_t PART(launch_msm_jac_sum_to_affine)(int grp, const uint32_t* parts, si
   hipError_t launch_msm_to_kernel_layout##SUF(int, const uint32_t*, uint32_t*, uint8_t*, size_t, hipStream_t); \
   hipError_t launch_msm_precompute##SUF(int, uint32_t*, uint8_t*, size_t, int, int, uint32_t*, hipStream_t); \
   hipError_t launch_msm_sort##SUF(const MsmPlan&, const uint8_t*, const uint32_t*, void*, hipStream_t); \
+  hipError_t launch_msm_sort_batch##SUF(const MsmPlan&, const uint8_t*, const uint32_t*, size_t, void*, hipStream_t); \
   hipError_t launch_msm_accumulate##SUF(const MsmPlan&, const uint32_t*, void*, hipStream_t); \
   hipError_t launch_msm_reduce##SUF(const MsmPlan&, void*, uint32_t*, uint32_t*, hipStream_t); \
   hipError_t launch_msm_jac_add##SUF(int, const uint32_t*, const uint32_t*, uint32_t*, hipStream_t); \
@@ -849,10 +942,21 @@ ZKT_MSM_FWD(_other) ZKT_MSM_FWD(_secp)
 hipError_t launch_msm_to_kernel_layout(int grp, const uint32_t* a, uint32_t* t, uint8_t* i, size_t n, hipStream_t s) { return ZKT_MSM_BY_GROUP(grp, launch_msm_to_kernel_layout, grp, a, t, i, n, s); }
 hipError_t launch_msm_precompute(int grp, uint32_t* t, uint8_t* i, size_t n, int c, int nw, uint32_t* tmp, hipStream_t s) { return ZKT_MSM_BY_GROUP(grp, launch_msm_precompute, grp, t, i, n, c, nw, tmp, s); }
 hipError_t launch_msm_sort(const MsmPlan& P, const uint8_t* i, const uint32_t* k, void* w, hipStream_t s) { return ZKT_MSM_BY_GROUP(P.grp, launch_msm_sort, P, i, k, w, s); }
+hipError_t launch_msm_sort_batch(const MsmPlan& P, const uint8_t* i, const uint32_t* k, size_t st, void* w, hipStream_t s) { return ZKT_MSM_BY_GROUP(P.grp, launch_msm_sort_batch, P, i, k, st, w, s); }
 hipError_t launch_msm_accumulate(const MsmPlan& P, const uint32_t* t, void* w, hipStream_t s) { return ZKT_MSM_BY_GROUP(P.grp, launch_msm_accumulate, P, t, w, s); }
 hipError_t launch_msm_reduce(const MsmPlan& P, void* w, uint32_t* j, uint32_t* o, hipStream_t s) { return ZKT_MSM_BY_GROUP(P.grp, launch_msm_reduce, P, w, j, o, s); }
 hipError_t launch_msm_jac_add(int grp, const uint32_t* a, const uint32_t* b, uint32_t* o, hipStream_t s) { return ZKT_MSM_BY_GROUP(grp, launch_msm_jac_add, grp, a, b, o, s); }
 hipError_t launch_msm_jac_sum_to_affine(int grp, const uint32_t* p, size_t c, size_t st, uint32_t* o, hipStream_t s) { return ZKT_MSM_BY_GROUP(grp, launch_msm_jac_sum_to_affine, grp, p, c, st, o, s); }
+// Batched form: k scalar vectors over ONE resident base set.  The handle's table was built for msm_plan's c / nwin, so the width is that plan's; vector v owns
+// bucket set v (2^(c-1) buckets each, k sets side by side in one workspace), and the task granularity is picked over all k * nwin * n digits: the point of the form
+// is that k latency-bound slivers become one grid.  The workspace is what the carve hands out for this plan (no partition-sort scratch).
+MsmPlan msm_plan_batch(size_t n, int grp, int k) {
+  MsmPlan p = msm_plan(n, grp);
+  p.batch = k; p.half = size_t(1) << (p.c - 1); p.nbuckets = (size_t)k * p.half;
+  p.chunk = pick_chunk((size_t)k * p.nwin * n, grp);
+  p.ws_bytes = (size_t)(carve(p, nullptr).end - (uint8_t*)nullptr) + 4096;
+  return p;
+}
 #endif
 
 }  // namespace zkt
