@@ -30,6 +30,10 @@
  * staging stream; calls on one handle (bases, proving key, context) are serialised by a per-handle lock (submit / collect of different
  * slots of one handle may be issued from different threads).  No host pointer is retained past return.  There is NO CPU fallback:
  * without a HIP device every compute entry point returns ZKT_ERR_DEVICE.
+ * The polynomial entry points (zkt_fr_poly_*, zkt_qap_*, zkt_groth16_prove_qap) keep one pair of twiddle tables per transform size 2^k they have used
+ * (2^k * 32 + 32 bytes, built under a lock at the first call that needs the size, released by zkt_shutdown).  After that first call at a size,
+ * zkt_fr_poly_mul_dev allocates nothing but its scratch: two stream-ordered buffers of 2^k elements (one when squaring), taken with hipMallocAsync and given
+ * back with hipFreeAsync on the caller's stream; the direct path (a short operand) allocates nothing at all.
  *
  * `_dev` variants take DEVICE pointers in the same layouts plus a hipStream_t (as void*)
  * and are asynchronous on that stream except where they return a host result.
@@ -47,6 +51,7 @@ extern "C" {
 #define ZKT_ERR_INFINITY 2   /* pairing argument at infinity */
 #define ZKT_ERR_SHAPE 3      /* bad size / null pointer / index mismatch (polynomial.rs:277-279) */
 #define ZKT_ERR_DEVICE 4     /* no HIP device, HIP error, or library not initialised */
+#define ZKT_ERR_REMAINDER 5  /* a division that the reference requires to be exact left a remainder ("p should be divisible by t", prover.rs:67-70) */
 
 typedef struct { uint64_t x[6], y[6]; uint32_t is_infinity, _pad; } zkt_g1_affine;    /* 104 B */
 typedef struct { uint64_t x[12], y[12]; uint32_t is_infinity, _pad; } zkt_g2_affine;  /* 200 B; x = {u1,u0} */
@@ -54,7 +59,7 @@ typedef struct { uint64_t x[4], y[4]; uint32_t is_infinity, _pad; } zkt_secp_aff
 
 /* lifecycle — mcl_initializer.rs:4-15 (init once, panic on failure) */
 int zkt_init(int device);                 /* device = HIP ordinal, -1 = current */
-void zkt_shutdown(void);                  /* releases everything bound to the device of this zkt_init: the communicator of zkt_comm_init (zkt_comm_finalize), the last one-shot Bulletproofs context, the statement tables of the last four Groth16 keys, the io-point tables of the last two Pinocchio keys, the comb tables of the two BLS12-381 generators and the library's side stream.  Handles the caller still owns (zkt_*_bases, contexts, keys) must be freed BEFORE it.  zkt_init may then be called again, on the same or another device */
+void zkt_shutdown(void);                  /* releases everything bound to the device of this zkt_init: the communicator of zkt_comm_init (zkt_comm_finalize), the last one-shot Bulletproofs context, the statement tables of the last four Groth16 keys, the io-point tables of the last two Pinocchio keys, the twiddle tables of the polynomial entry points (zkt_fr_poly_*, zkt_qap_*), the comb tables of the two BLS12-381 generators and the library's side stream.  Handles the caller still owns (zkt_*_bases, contexts, keys) must be freed BEFORE it.  zkt_init may then be called again, on the same or another device */
 int zkt_version(void);
 const char* zkt_strerror(int status);
 size_t zkt_last_error_index(void);        /* thread-local; valid after a non-OK return */
@@ -239,6 +244,38 @@ int zkt_groth16_vk_prepare(const zkt_groth16_crs* crs, size_t n_stmt);
 /* returns 1 accept, 0 reject, negative = -status (a pairing argument at infinity panics in the reference) */
 int zkt_groth16_verify(const zkt_groth16_crs* crs, const zkt_g1_affine* A, const zkt_g2_affine* B, const zkt_g1_affine* C,
                        const uint64_t* stmt_wires, size_t n_stmt);
+
+/* Dense polynomials over Fr (field/polynomial.rs): coefficients low degree first, 4 limbs each; a limb vector that is not below r is reduced on load as
+ * PrimeFieldElem::new does (prime_field_elem.rs:263-272); outputs are canonical.  Blocking, host pointers (except _dev); no input may alias an output.
+ * No operand and no result may have more than ZKT_POLY_MAX_LEN coefficients: more is ZKT_ERR_SHAPE before anything is allocated or launched.
+ * Products run one lane per output coefficient when an operand is short and through exact Fr transforms (2-adicity 32) otherwise; division is a Newton
+ * inversion of the reversed divisor.  Quotient and remainder are unique, so the results are the reference's loops' bit for bit. */
+#define ZKT_POLY_MAX_LEN ((size_t)1 << 21)   /* coefficients of any operand and of any result */
+/* Polynomial::multiply_by polynomial.rs:173-190: exactly na + nb - 1 coefficients, NOT normalised (a zero operand gives na + nb - 1 zeros, as the reference
+ * does).  na == 0, nb == 0 or a null pointer: ZKT_ERR_SHAPE.  a == b with na == nb is a squaring. */
+int zkt_fr_poly_mul(const uint64_t* a, size_t na, const uint64_t* b, size_t nb, uint64_t* out /* na+nb-1 */);
+/* the same on device pointers (32-byte aligned), asynchronous on `stream` (a hipStream_t) */
+int zkt_fr_poly_mul_dev(const uint64_t* dev_a, size_t na, const uint64_t* dev_b, size_t nb, uint64_t* dev_out, void* stream);
+/* Polynomial::divide_by polynomial.rs:204-238: q gets exactly na - nb + 1 coefficients (zero high ones when a has zero leading coefficients); rem gets
+ * a - q b in all nb - 1 slots, *rem_len = its length with trailing zeros trimmed, 0 = DivResult::Quotient.  na < nb (the subtraction at :207 underflows) or a
+ * leading coefficient of b that is zero mod r (the assert at :209): ZKT_ERR_SHAPE with zkt_last_error_index() == nb - 1. */
+int zkt_fr_poly_divrem(const uint64_t* a, size_t na, const uint64_t* b, size_t nb,
+                       uint64_t* q /* na-nb+1 */, uint64_t* rem /* nb-1; NULL allowed iff nb == 1 */, size_t* rem_len);
+/* Polynomial::eval_at polynomial.rs:240-249 at k points (eval_from_1_to_n :251-262 is xs = 1..n).  n == 0: ZKT_ERR_SHAPE; k == 0: ZKT_OK. */
+int zkt_fr_poly_eval_batch(const uint64_t* coeffs, size_t n, const uint64_t* xs, size_t k, uint64_t* out /* k */);
+/* QAP::build_t qap/qap.rs:115-135: the n + 1 coefficients of prod_{i=1..n} (x - i); n == 0 gives [1]. */
+int zkt_qap_build_t(size_t n, uint64_t* out /* n+1 */);
+/* QAP::build_p qap.rs:99-112 and its division by t in Prover::new (groth16/zktoolkit_based/prover.rs:64-71): ui, vi, wi are rows x n dense arrays as
+ * zkt_groth16_prove takes them, p = (sum wires[i] ui[i]) (sum wires[i] vi[i]) - sum wires[i] wi[i] has 2n - 1 coefficients, and h gets the n - 1 coefficients
+ * of the reference's un-normalised quotient p / t (for n == 1 nothing is written and the call is OK iff p == 0).  A non-zero remainder:
+ * ZKT_ERR_REMAINDER with zkt_last_error_index() = the remainder's degree.  The same call serves Pinocchio's vi, wi, yi (pinocchio/prover.rs:50-96). */
+int zkt_qap_quotient(const uint64_t* ui, const uint64_t* vi, const uint64_t* wi, size_t rows, size_t n,
+                     const uint64_t* wires /* rows */, uint64_t* h /* n-1 */);
+/* Prover::new + Prover::prove (prover.rs:50-147): ui, vi, wi ((m+1) x n) and the wires are uploaded once, h is computed on the device, and (A, B, C) are
+ * byte-identical to zkt_groth16_prove called with that h.  ZKT_ERR_REMAINDER (+ index) as for zkt_qap_quotient, with A, B, C untouched. */
+int zkt_groth16_prove_qap(const zkt_groth16_crs* crs, const uint64_t* ui, const uint64_t* vi, const uint64_t* wi,
+                          const uint64_t* wires, const uint64_t* r, const uint64_t* s,
+                          zkt_g1_affine* A, zkt_g2_affine* B, zkt_g1_affine* C);
 
 /* f-4: equalities of pairing products as the reference's callers test them (lhs == rhs on GTPoints: signature.rs:34-39,
  * pinocchio/verifier.rs:43-84).  For each of n elements: prod_{j<k} tate(+-g1[i*k+j], g2[i*k+j]) == 1, k <= 4; negate[j] != 0

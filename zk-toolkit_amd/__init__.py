@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ZKT_LIB_PATH", os.path.join(_HERE, "libzkt_hip.so"))   # override only for A/B experiments
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "zkt.h")
 
-ZKT_OK, ZKT_ERR_INV_ZERO, ZKT_ERR_INFINITY, ZKT_ERR_SHAPE, ZKT_ERR_DEVICE = 0, 1, 2, 3, 4
+ZKT_OK, ZKT_ERR_INV_ZERO, ZKT_ERR_INFINITY, ZKT_ERR_SHAPE, ZKT_ERR_DEVICE, ZKT_ERR_REMAINDER = 0, 1, 2, 3, 4, 5
 G1_WORDS64, G2_WORDS64, FQ12_WORDS64 = 13, 25, 72
 G1_PARTIAL_WORDS, G2_PARTIAL_WORDS, SECP_PARTIAL_WORDS = 42, 84, 24
 GROTH16_PARTIAL_WORDS = 2 * G1_PARTIAL_WORDS + G2_PARTIAL_WORDS   # ZKT_*_PARTIAL_WORDS: u32 words of one opaque Jacobian partial
@@ -92,6 +92,13 @@ def lib():
         L.zkt_bp_ipa_ctx_free.argtypes = [vp]; L.zkt_bp_ipa_ctx_free.restype = None
         L.zkt_bp_inner_product_argument_ctx.argtypes = [vp] * 6
         L.zkt_bp_range_proof_ctx.argtypes = [vp] * 6 + [ctypes.c_int] + [vp] * 3
+        L.zkt_fr_poly_mul.argtypes = [vp, sz, vp, sz, vp]
+        L.zkt_fr_poly_mul_dev.argtypes = [vp, sz, vp, sz, vp, vp]
+        L.zkt_fr_poly_divrem.argtypes = [vp, sz, vp, sz, vp, vp, vp]
+        L.zkt_fr_poly_eval_batch.argtypes = [vp, sz, vp, sz, vp]
+        L.zkt_qap_build_t.argtypes = [sz, vp]
+        L.zkt_qap_quotient.argtypes = [vp, vp, vp, sz, sz, vp, vp]
+        L.zkt_groth16_prove_qap.argtypes = [vp] * 10
         _lib = L
     return _lib
 
@@ -104,7 +111,7 @@ def init(device=-1):
 
 def check(rc):
     if rc != ZKT_OK:
-        raise ZktError(rc, lib().zkt_last_error_index() if rc in (ZKT_ERR_INV_ZERO, ZKT_ERR_INFINITY) else None)
+        raise ZktError(rc, lib().zkt_last_error_index() if rc in (ZKT_ERR_INV_ZERO, ZKT_ERR_INFINITY, ZKT_ERR_REMAINDER) else None)
 
 
 def exported_symbols():

@@ -241,6 +241,7 @@ const char* zkt_strerror(int s) {
     case ZKT_ERR_INFINITY: return "pairing argument is the point at infinity";
     case ZKT_ERR_SHAPE: return "bad size, null pointer or non-canonical input";
     case ZKT_ERR_DEVICE: return "no HIP device / HIP error / zkt_init not called";
+    case ZKT_ERR_REMAINDER: return "p should be divisible by t";
   }
   return "unknown";
 }
@@ -267,6 +268,7 @@ static void tate_events_release();
 void zkt_shutdown(void) {
   if (g.ready) (void)hipSetDevice(g.device);
   zkt_comm_finalize();                                // the communicator and its buffers live on this device
+  zkt_poly_clear_caches();                            // twiddle tables of the polynomial entry points
   zkt_internal_clear_caches();                        // before g.mu is taken: releasing a cached context frees base sets, which lock it themselves
   std::lock_guard<std::mutex> lk(g.mu);
   if (!g.ready) return;

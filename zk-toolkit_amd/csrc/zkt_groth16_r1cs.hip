@@ -387,6 +387,27 @@ int upload_csr(const zkt_sparse_rows* M, size_t n, size_t cols, Csr& rowwise, Cs
 }
 }  // namespace
 
+// ---- the transform for other translation units (zkt_internal.h; csrc/zkt_poly.hip is the caller) -------------------------------------
+int zkt_fr_ntt_forward(uint32_t* a, int logN, const uint32_t* tw, const uint32_t* mulvec, hipStream_t s, size_t batch) { return ntt_forward(a, logN, tw, mulvec, s, batch); }
+int zkt_fr_ntt_inverse(uint32_t* a, int logN, const uint32_t* twinv, hipStream_t s, size_t batch) { return ntt_inverse(a, logN, twinv, s, batch); }
+int zkt_fr_scan_mul(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) { return scan_mul(in, out, n, s); }
+// tw[k] = w^k and twinv[k] = w^-k for k < N/2, w of order N = 2^logN (Montgomery), and ninv = 1/N; blocking
+int zkt_fr_ntt_twiddles(int logN, uint32_t* tw, uint32_t* twinv, uint32_t* ninv, hipStream_t s) {
+  if (logN < 1 || logN > FR_TWO_ADICITY) return ZKT_ERR_SHAPE;
+  const size_t half = (size_t)1 << (logN - 1);
+  uint64_t ones[20] = {0}; for (int k = 0; k < 5; ++k) ones[4 * k] = 1;             // k_setup_consts inverts two of its five inputs
+  Dev dtrap, consts; ZCHK(dtrap.alloc(160)); ZCHK(consts.alloc(K_COUNT * FRB));
+  ZCHK(up(dtrap, ones, 160, s));
+  hipLaunchKernelGGL(k_setup_consts, dim3(1), dim3(64), 0, s, (const uint32_t*)dtrap.w(), consts.w(), logN);
+  hipLaunchKernelGGL(k_fill_pow, dim3(grid_blocks(half)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_OMEGA * FW), tw, half);
+  ZCHK(scan_mul(tw, tw, half, s));
+  hipLaunchKernelGGL(k_fill_pow, dim3(grid_blocks(half)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_OMEGA_INV * FW), twinv, half);
+  ZCHK(scan_mul(twinv, twinv, half, s));
+  HIPCHK(hipMemcpyAsync(ninv, consts.w() + K_NINV * FW, FRB, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return ZKT_OK;
+}
+
 struct zkt_groth16_pk {
   size_t n = 0, l = 0, m = 0;
   // the quotient's blocked convolution (k_recip_blocks): this rank's cnt = hiC2 - loC2 values h(n+s), s = qs0 .. qs0+cnt-1, from Q input blocks of Bi, transforms of size M = 2 Bi
