@@ -15,7 +15,7 @@ R = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 POLY_DIRECT_MAX = 64
 POLY_DIV_DIRECT_MAX = 64
 POLY_MAX_LEN = 1 << 21
-NTT_TILE_LOG = 10               # zkt_groth16_r1cs.hip: the contiguous launch covers up to 10 stages, strided launches up to 8 each
+NTT_TILE_LOG = 10               # zkt_fr_vec.hip: the contiguous launch covers up to 10 stages, strided launches up to 8 each
 NTT_MAX_STAGES = 8
 EVAL_ITEMS, EVAL_TPB = 16, 256
 EVAL_CHUNK = EVAL_ITEMS * EVAL_TPB

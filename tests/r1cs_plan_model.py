@@ -8,6 +8,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "zk-toolkit_amd", "csrc", "zkt_groth16_r1cs.hip")
+FR_SRC = os.path.join(ROOT, "zk-toolkit_amd", "csrc", "zkt_fr_vec.hip")      # the transform and the scan
 
 NTT_TILE_LOG = 10           # a k_ntt_group tile holds at most 2^10 elements (32 KB of LDS)
 NTT_MAX_STAGES = 8          # stages per strided launch
@@ -20,7 +21,7 @@ MAX_N = (SC_TILE * SC_TILE - 1) // 2      # 2n + 1 factorials must fit the two-l
 
 def library_constants():
     """the same constants as the library source writes them"""
-    with open(SRC) as f:
+    with open(FR_SRC) as f:
         text = f.read()
     def one(pattern):
         m = re.findall(pattern, text)
@@ -29,9 +30,11 @@ def library_constants():
     tile_log = int(one(r"static constexpr int NTT_TILE_LOG = (\d+), NTT_TPB = \d+;"))
     cap = one(r"int cnt = rem < (\d+) \? rem : (\d+), cb = NTT_TILE_LOG - cnt;")
     assert cap[0] == cap[1], cap
+    tpb, items = one(r"static constexpr int SC_TPB = (\d+), SC_ITEMS = (\d+), SC_TILE = SC_TPB \* SC_ITEMS;")
+    with open(SRC) as f:
+        text = f.read()
     clause = int(one(r"\(logM <= (\d+) && \(\(size_t\)1 << \(logM - 1\)\) < n\)"))
     spmv_long = int(one(r"static constexpr uint32_t SPMV_LONG = (\d+);"))
-    tpb, items = one(r"static constexpr int SC_TPB = (\d+), SC_ITEMS = (\d+), SC_TILE = SC_TPB \* SC_ITEMS;")
     side = int(one(r"pk->hiC2 - pk->loC2\) < \(\(size_t\)1 << (\d+)\);"))
     one(r"n > ZKT_R1CS_MAX_N")                      # the setup checks the header's limit
     with open(os.path.join(ROOT, "include", "zkt.h")) as f:

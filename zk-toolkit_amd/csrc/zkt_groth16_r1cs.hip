@@ -31,19 +31,13 @@
 #include <mutex>
 #include <cstring>
 #include <cstdio>
-#include "abi.h"
+#include "fr_vec.h"
 #include "zkt_internal.h"
 #include "../../include/zkt.h"
 #include "host_abi.h"
 
 namespace zkt {
 typedef FrC C;
-typedef Fp<FrC> Fr;
-static constexpr int FW = 8;          // u32 words of an Fr element (canonical and Montgomery alike)
-
-__device__ inline Fr ldm(const uint32_t* p) { return ld_raw<C>(p); }       // Montgomery in memory
-__device__ inline void stm(uint32_t* p, const Fr& a) { st_raw<C>(p, a); }
-__device__ inline Fr fr_small(uint32_t k) { uint32_t w[8] = {k, 0, 0, 0, 0, 0, 0, 0}; return fp_from_words<C>(w); }
 
 // ---- elementwise helpers ------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_to_mont(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n) {
@@ -69,36 +63,6 @@ __global__ void __launch_bounds__(256) k_iota(uint32_t* __restrict__ out, size_t
 __global__ void __launch_bounds__(256) k_x_minus(const uint32_t* __restrict__ consts, uint32_t* __restrict__ out, size_t cnt) {
   size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= cnt) return;
   stm(out + i * FW, fp_sub(ldm(consts), fr_small((uint32_t)(i + 1))));
-}
-// out[0] = 1, out[k>0] = w   (prefix product = w^k)
-__global__ void __launch_bounds__(256) k_fill_pow(const uint32_t* __restrict__ w, uint32_t* __restrict__ out, size_t n) {
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= n) return;
-  stm(out + i * FW, i ? ldm(w) : fp_one<C>());
-}
-
-// ---- inclusive prefix product (factorials, prod (x - j), twiddle tables) ------------------------------------------
-static constexpr int SC_TPB = 256, SC_ITEMS = 8, SC_TILE = SC_TPB * SC_ITEMS;
-__global__ void __launch_bounds__(SC_TPB) k_scanmul_tile(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n, uint32_t* __restrict__ tile_total) {
-  __shared__ uint32_t lds[SC_TPB * FW];
-  const int t = threadIdx.x;
-  const size_t base = (size_t)blockIdx.x * SC_TILE + (size_t)t * SC_ITEMS;
-  Fr loc[SC_ITEMS]; Fr run = fp_one<C>();
-#pragma unroll
-  for (int k = 0; k < SC_ITEMS; ++k) { if (base + k < n) run = fp_mul(run, ldm(in + (base + k) * FW)); loc[k] = run; }
-  stm(lds + t * FW, run); __syncthreads();
-  for (int d = 1; d < SC_TPB; d <<= 1) {                 // Hillis-Steele over the 256 thread totals
-    Fr o = t >= d ? ldm(lds + (t - d) * FW) : fp_one<C>(); __syncthreads();
-    if (t >= d) { run = fp_mul(o, run); stm(lds + t * FW, run); } __syncthreads();
-  }
-  Fr excl = t ? ldm(lds + (t - 1) * FW) : fp_one<C>();
-#pragma unroll
-  for (int k = 0; k < SC_ITEMS; ++k) if (base + k < n) stm(out + (base + k) * FW, fp_mul(excl, loc[k]));
-  if (t == SC_TPB - 1) stm(tile_total + (size_t)blockIdx.x * FW, run);
-}
-__global__ void __launch_bounds__(256) k_scanmul_apply(uint32_t* __restrict__ data, size_t n, const uint32_t* __restrict__ tile_prefix) {
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= n) return;
-  size_t tile = i / SC_TILE; if (tile == 0) return;
-  stm(data + i * FW, fp_mul(ldm(tile_prefix + (tile - 1) * FW), ldm(data + i * FW)));
 }
 
 // ---- CSR mat-vec in Fr (Montgomery): out[r] = sum_k val[k] * vec[idx[k]] ---------------------------------------------
@@ -130,21 +94,12 @@ __global__ void __launch_bounds__(256) k_spmv_long(const uint32_t* __restrict__ 
 
 // ---- setup scalars ----------------------------------------------------------------------------------------
 // consts layout (Montgomery, 8 words each)
-enum { K_X = 0, K_ALPHA, K_BETA, K_GINV, K_DINV, K_TX, K_TE, K_HB, K_OMEGA, K_OMEGA_INV, K_NINV, K_COUNT };
-__global__ void k_setup_consts(const uint32_t* __restrict__ trap /*alpha,beta,gamma,delta,x canonical*/, uint32_t* __restrict__ consts, int logN) {
+enum { K_X = 0, K_ALPHA, K_BETA, K_GINV, K_DINV, K_TX, K_TE, K_HB, K_COUNT };
+__global__ void k_setup_consts(const uint32_t* __restrict__ trap /*alpha,beta,gamma,delta,x canonical*/, uint32_t* __restrict__ consts) {
   if (threadIdx.x || blockIdx.x) return;
   stm(consts + K_ALPHA * FW, ld_fp<C>(trap)); stm(consts + K_BETA * FW, ld_fp<C>(trap + 8));
   stm(consts + K_GINV * FW, fp_inv(ld_fp<C>(trap + 16))); stm(consts + K_DINV * FW, fp_inv(ld_fp<C>(trap + 24)));
   stm(consts + K_X * FW, ld_fp<C>(trap + 32));
-  uint32_t rw[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) rw[i] = fr_root_word(i);
-  Fr w = fp_from_words<C>(rw);
-  for (int k = FR_TWO_ADICITY; k > logN; --k) w = fp_sqr(w);                      // order 2^logN
-  stm(consts + K_OMEGA * FW, w); stm(consts + K_OMEGA_INV * FW, fp_inv(w));
-  Fr two = fr_small(2), nn = fp_one<C>();
-  for (int k = 0; k < logN; ++k) nn = fp_mul(nn, two);
-  stm(consts + K_NINV * FW, fp_inv(nn));
 }
 // after the prefix product of (x - j): t(x) = pre[n-1], T_E(x) = pre[2n-2] / pre[n-1], hb = t(x) T_E(x) / delta
 __global__ void k_setup_consts2(const uint32_t* __restrict__ pre, size_t n, uint32_t* __restrict__ consts) {
@@ -197,58 +152,6 @@ __global__ void __launch_bounds__(256) k_uvw(const uint32_t* __restrict__ consts
   st_fp<C>(y_canon + i * FW, fp_mul(s, ldm(consts + (i <= l ? K_GINV : K_DINV) * FW)));
 }
 
-// ---- Fr NTT of size N = 2^logN ------------------------------------------------------------------------------------
-// forward = decimation in frequency (natural order in, bit-reversed out); inverse = decimation in time on the
-// bit-reversed spectrum (natural order out), so no reordering pass exists; the 1/N lives in the precomputed kernel spectrum.
-// HBM-bound (one butterfly = one Fr multiply per 64 B moved), so stages are fused through LDS: a launch runs `cnt`
-// consecutive radix-2 stages (butterfly distances 2^lo .. 2^(lo+cnt-1)) on a tile of 2^cnt strided rows x 2^cbits
-// adjacent columns (<= 1024 elements, 32 KB), every element read and written once per launch, rows of >= 128 B contiguous.
-// logN = 21 is three launches per transform (10 + 8 + 3 stages) instead of 21.
-// A launch covers any number of transforms of the same size: consecutive ones simply continue blockIdx.x (the twiddle of a butterfly depends on its position
-// inside its group only), blockIdx.y steps over arrays `ystride` elements apart.  `mulvec` is indexed like the consecutive transforms of one array.
-// (one-wave workgroups for the transform were measured at the end of round 3, in case its four-wave workgroups were what starved beside an accumulate grid: 9.1 ms against 7.6
-// for a shard of a proof, 40 against 50 proofs/s on one GPU — not that)
-static constexpr int NTT_TILE_LOG = 10, NTT_TPB = 256;
-template <bool DIF>
-__global__ void __launch_bounds__(NTT_TPB) k_ntt_group(uint32_t* __restrict__ a, int logN, int lo, int cnt, int cbits, const uint32_t* __restrict__ tw,
-                                                       const uint32_t* __restrict__ mulvec, size_t ystride) {
-  __shared__ uint32_t lds[(1 << NTT_TILE_LOG) * FW];
-  a += (size_t)blockIdx.y * ystride * FW;                         // grid.y: independent arrays (the three polynomials), sharing `mulvec`
-  const int tile = 1 << (cnt + cbits), cmask = (1 << cbits) - 1;
-  const size_t tiles_per_hi = (size_t)1 << (lo - cbits);
-  const size_t hi = blockIdx.x / tiles_per_hi, c0 = (blockIdx.x % tiles_per_hi) << cbits;
-  const size_t gbase = (hi << (lo + cnt)) | c0;
-  for (int e = threadIdx.x; e < tile; e += NTT_TPB) {
-    const size_t g = gbase | ((size_t)(e >> cbits) << lo) | (size_t)(e & cmask);
-    const uint4* src = reinterpret_cast<const uint4*>(a + g * FW);
-    uint4* dst = reinterpret_cast<uint4*>(lds + e * FW);
-    dst[0] = src[0]; dst[1] = src[1];
-  }
-  __syncthreads();
-  for (int st = 0; st < cnt; ++st) {
-    const int t = DIF ? cnt - 1 - st : st;                       // local butterfly distance 2^t rows
-    for (int b = threadIdx.x; b < tile / 2; b += NTT_TPB) {
-      const int cc = b & cmask, kb = b >> cbits;
-      const int k0 = ((kb >> t) << (t + 1)) | (kb & ((1 << t) - 1));
-      const int e0 = (k0 << cbits) | cc, e1 = e0 + (1 << (t + cbits));
-      const size_t j = ((size_t)(k0 & ((1 << t) - 1)) << lo) | c0 | (size_t)cc;      // position inside the butterfly group
-      const Fr w = ldm(tw + (j << (logN - 1 - lo - t)) * FW);
-      Fr u = ldm(lds + e0 * FW), v = ldm(lds + e1 * FW);
-      if (DIF) { stm(lds + e0 * FW, fp_add(u, v)); stm(lds + e1 * FW, fp_mul(fp_sub(u, v), w)); }
-      else { v = fp_mul(v, w); stm(lds + e0 * FW, fp_add(u, v)); stm(lds + e1 * FW, fp_sub(u, v)); }
-    }
-    __syncthreads();
-  }
-  for (int e = threadIdx.x; e < tile; e += NTT_TPB) {
-    const size_t g = gbase | ((size_t)(e >> cbits) << lo) | (size_t)(e & cmask);
-    if (mulvec) stm(a + g * FW, fp_mul(ldm(lds + e * FW), ldm(mulvec + g * FW)));      // fused pointwise product with a spectrum
-    else {
-      const uint4* src = reinterpret_cast<const uint4*>(lds + e * FW);
-      uint4* dst = reinterpret_cast<uint4*>(a + g * FW);
-      dst[0] = src[0]; dst[1] = src[1];
-    }
-  }
-}
 __global__ void __launch_bounds__(256) k_scale_all(uint32_t* __restrict__ a, const uint32_t* __restrict__ s, size_t n) {
   size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= n) return;
   stm(a + i * FW, fp_mul(ldm(a + i * FW), ldm(s)));
@@ -308,46 +211,6 @@ using namespace zkt;
 namespace {
 struct Csr { Dev ptr, idx, val, long_rows; size_t rows = 0, nnz = 0, n_long = 0; };
 
-// inclusive prefix product, in place allowed (in == out); two levels of tiles cover 2048^2 elements
-int scan_mul(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) {
-  if (n == 0) return ZKT_OK;
-  const size_t tiles = (n + SC_TILE - 1) / SC_TILE;
-  if (tiles > (size_t)SC_TILE) return ZKT_ERR_SHAPE;
-  Dev tot, tot2; ZCHK(tot.alloc(tiles * FRB)); ZCHK(tot2.alloc(FRB));
-  hipLaunchKernelGGL(k_scanmul_tile, dim3((unsigned)tiles), dim3(SC_TPB), 0, s, in, out, n, tot.w());
-  if (tiles > 1) {
-    hipLaunchKernelGGL(k_scanmul_tile, dim3(1), dim3(SC_TPB), 0, s, (const uint32_t*)tot.w(), tot.w(), tiles, tot2.w());
-    hipLaunchKernelGGL(k_scanmul_apply, dim3(grid_blocks(n)), dim3(256), 0, s, out, n, (const uint32_t*)tot.w());
-  }
-  HIPCHK(hipStreamSynchronize(s));     // the tile totals die with this frame
-  return ZKT_OK;
-}
-// stage groups: the contiguous one first (distances 1..2^(c0-1)), then strided groups of <= 8 stages with >= 4 adjacent columns
-struct NttGroup { int lo, cnt, cbits; };
-int ntt_groups(int logN, NttGroup* g) {
-  int k = 0, c0 = logN < NTT_TILE_LOG ? logN : NTT_TILE_LOG;
-  g[k++] = {0, c0, 0};
-  for (int lo = c0, rem = logN - c0; rem > 0;) {
-    int cnt = rem < 8 ? rem : 8, cb = NTT_TILE_LOG - cnt; if (cb > lo) cb = lo;
-    g[k++] = {lo, cnt, cb}; lo += cnt; rem -= cnt;
-  }
-  return k;
-}
-// forward: natural -> bit-reversed; if `mulvec`, the spectrum is multiplied by it on the way out.  `batch` consecutive transforms per array, `ny` arrays `ystride` elements apart.
-int ntt_forward(uint32_t* a, int logN, const uint32_t* tw, const uint32_t* mulvec, hipStream_t s, size_t batch = 1, unsigned ny = 1, size_t ystride = 0) {
-  NttGroup g[8]; const int k = ntt_groups(logN, g);
-  for (int i = k - 1; i >= 0; --i)
-    hipLaunchKernelGGL(k_ntt_group<true>, dim3((unsigned)((batch << logN) >> (g[i].cnt + g[i].cbits)), ny), dim3(NTT_TPB), 0, s, a, logN, g[i].lo, g[i].cnt, g[i].cbits, tw,
-                       i == 0 ? mulvec : (const uint32_t*)nullptr, ystride);
-  HIPCHK(hipGetLastError()); return ZKT_OK;
-}
-int ntt_inverse(uint32_t* a, int logN, const uint32_t* twinv, hipStream_t s, size_t batch = 1, unsigned ny = 1, size_t ystride = 0) {
-  NttGroup g[8]; const int k = ntt_groups(logN, g);
-  for (int i = 0; i < k; ++i)
-    hipLaunchKernelGGL(k_ntt_group<false>, dim3((unsigned)((batch << logN) >> (g[i].cnt + g[i].cbits)), ny), dim3(NTT_TPB), 0, s, a, logN, g[i].lo, g[i].cnt, g[i].cbits, twinv,
-                       (const uint32_t*)nullptr, ystride);
-  HIPCHK(hipGetLastError()); return ZKT_OK;
-}
 void spmv(const Csr& M, const uint32_t* vec, uint32_t* out, hipStream_t s) {
   hipLaunchKernelGGL(k_spmv, dim3(grid_blocks(M.rows)), dim3(256), 0, s, (const uint32_t*)M.ptr.w(), (const uint32_t*)M.idx.w(), (const uint32_t*)M.val.w(), vec, out, M.rows);
   if (M.n_long) hipLaunchKernelGGL(k_spmv_long, dim3((unsigned)M.n_long), dim3(256), 0, s, (const uint32_t*)M.ptr.w(), (const uint32_t*)M.idx.w(), (const uint32_t*)M.val.w(), vec, out, (const uint32_t*)M.long_rows.w());
@@ -386,27 +249,6 @@ int upload_csr(const zkt_sparse_rows* M, size_t n, size_t cols, Csr& rowwise, Cs
   return ZKT_OK;
 }
 }  // namespace
-
-// ---- the transform for other translation units (zkt_internal.h; csrc/zkt_poly.hip is the caller) -------------------------------------
-int zkt_fr_ntt_forward(uint32_t* a, int logN, const uint32_t* tw, const uint32_t* mulvec, hipStream_t s, size_t batch) { return ntt_forward(a, logN, tw, mulvec, s, batch); }
-int zkt_fr_ntt_inverse(uint32_t* a, int logN, const uint32_t* twinv, hipStream_t s, size_t batch) { return ntt_inverse(a, logN, twinv, s, batch); }
-int zkt_fr_scan_mul(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) { return scan_mul(in, out, n, s); }
-// tw[k] = w^k and twinv[k] = w^-k for k < N/2, w of order N = 2^logN (Montgomery), and ninv = 1/N; blocking
-int zkt_fr_ntt_twiddles(int logN, uint32_t* tw, uint32_t* twinv, uint32_t* ninv, hipStream_t s) {
-  if (logN < 1 || logN > FR_TWO_ADICITY) return ZKT_ERR_SHAPE;
-  const size_t half = (size_t)1 << (logN - 1);
-  uint64_t ones[20] = {0}; for (int k = 0; k < 5; ++k) ones[4 * k] = 1;             // k_setup_consts inverts two of its five inputs
-  Dev dtrap, consts; ZCHK(dtrap.alloc(160)); ZCHK(consts.alloc(K_COUNT * FRB));
-  ZCHK(up(dtrap, ones, 160, s));
-  hipLaunchKernelGGL(k_setup_consts, dim3(1), dim3(64), 0, s, (const uint32_t*)dtrap.w(), consts.w(), logN);
-  hipLaunchKernelGGL(k_fill_pow, dim3(grid_blocks(half)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_OMEGA * FW), tw, half);
-  ZCHK(scan_mul(tw, tw, half, s));
-  hipLaunchKernelGGL(k_fill_pow, dim3(grid_blocks(half)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_OMEGA_INV * FW), twinv, half);
-  ZCHK(scan_mul(twinv, twinv, half, s));
-  HIPCHK(hipMemcpyAsync(ninv, consts.w() + K_NINV * FW, FRB, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return ZKT_OK;
-}
 
 struct zkt_groth16_pk {
   size_t n = 0, l = 0, m = 0;
@@ -471,21 +313,21 @@ int zkt_groth16_setup_r1cs_sharded(size_t n, size_t l, size_t m, const zkt_spars
   ZCHK(upload_csr(A, n, rows, pk->A, At, s)); ZCHK(upload_csr(B, n, rows, pk->B, Bt, s)); ZCHK(upload_csr(Cmat, n, rows, pk->Cm, Ct, s));
 
   // ---- Fr tables ----
-  Dev dtrap, consts, fact, invfact, xm, pre, xinv, Lm, Lc, hbc, derr;
-  ZCHK(dtrap.alloc(160)); ZCHK(consts.alloc(K_COUNT * FRB)); ZCHK(fact.alloc((2 * n + 1) * FRB)); ZCHK(invfact.alloc((2 * n + 1) * FRB));
+  Dev dtrap, consts, minv, fact, invfact, xm, pre, xinv, Lm, Lc, hbc, derr;
+  ZCHK(dtrap.alloc(160)); ZCHK(consts.alloc(K_COUNT * FRB)); ZCHK(minv.alloc(FRB)); ZCHK(fact.alloc((2 * n + 1) * FRB)); ZCHK(invfact.alloc((2 * n + 1) * FRB));
   ZCHK(xm.alloc((2 * n) * FRB)); ZCHK(pre.alloc((2 * n) * FRB)); ZCHK(xinv.alloc((2 * n) * FRB)); ZCHK(Lm.alloc(n * FRB)); ZCHK(Lc.alloc(n * FRB));
   ZCHK(hbc.alloc(n * FRB)); ZCHK(derr.alloc(8));
   ZCHK(pk->cinv.alloc(n * FRB)); ZCHK(pk->P.alloc(n * FRB)); ZCHK(pk->ghat.alloc(QM * FRB)); ZCHK(pk->tw.alloc(M / 2 * FRB)); ZCHK(pk->twinv.alloc(M / 2 * FRB));
   unsigned long long noerr = NO_ERR;
   ZCHK(up(derr, &noerr, 8, s));
   ZCHK(up(dtrap, trap, 160, s));
-  hipLaunchKernelGGL(k_setup_consts, dim3(1), dim3(64), 0, s, (const uint32_t*)dtrap.w(), consts.w(), logM);
+  hipLaunchKernelGGL(k_setup_consts, dim3(1), dim3(64), 0, s, (const uint32_t*)dtrap.w(), consts.w());
   hipLaunchKernelGGL(k_iota, dim3(grid_blocks(2 * n + 1)), dim3(256), 0, s, fact.w(), 2 * n + 1);
-  ZCHK(scan_mul(fact.w(), fact.w(), 2 * n + 1, s));
+  ZCHK(fr_scan_mul(fact.w(), fact.w(), 2 * n + 1, s));
   hipLaunchKernelGGL(k_inv, dim3(grid_blocks(2 * n + 1)), dim3(256), 0, s, (const uint32_t*)fact.w(), invfact.w(), 2 * n + 1, (unsigned long long*)derr.p);
   const size_t nx = 2 * n - 1;
   hipLaunchKernelGGL(k_x_minus, dim3(grid_blocks(nx)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_X * FW), xm.w(), nx);
-  ZCHK(scan_mul(xm.w(), pre.w(), nx, s));
+  ZCHK(fr_scan_mul(xm.w(), pre.w(), nx, s));
   hipLaunchKernelGGL(k_inv, dim3(grid_blocks(nx)), dim3(256), 0, s, (const uint32_t*)xm.w(), xinv.w(), nx, (unsigned long long*)derr.p);
   unsigned long long e = NO_ERR;
   ZCHK(down(&e, derr.p, 8, s)); HIPCHK(hipStreamSynchronize(s));
@@ -493,15 +335,11 @@ int zkt_groth16_setup_r1cs_sharded(size_t n, size_t l, size_t m, const zkt_spars
   hipLaunchKernelGGL(k_setup_consts2, dim3(1), dim3(64), 0, s, (const uint32_t*)pre.w(), n, consts.w());
   hipLaunchKernelGGL(k_lagrange, dim3(grid_blocks(n)), dim3(256), 0, s, (const uint32_t*)consts.w(), (const uint32_t*)invfact.w(), (const uint32_t*)xinv.w(), n, pk->cinv.w(), Lm.w(), Lc.w());
   if (n >= 2) hipLaunchKernelGGL(k_hbasis, dim3(grid_blocks(n - 1)), dim3(256), 0, s, (const uint32_t*)consts.w(), (const uint32_t*)fact.w(), (const uint32_t*)invfact.w(), (const uint32_t*)xinv.w(), n, hbc.w(), pk->P.w());
-  // twiddles: w^k and w^-k, k < M/2, as prefix products
-  hipLaunchKernelGGL(k_fill_pow, dim3(grid_blocks(M / 2)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_OMEGA * FW), pk->tw.w(), M / 2);
-  ZCHK(scan_mul(pk->tw.w(), pk->tw.w(), M / 2, s));
-  hipLaunchKernelGGL(k_fill_pow, dim3(grid_blocks(M / 2)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_OMEGA_INV * FW), pk->twinv.w(), M / 2);
-  ZCHK(scan_mul(pk->twinv.w(), pk->twinv.w(), M / 2, s));
+  ZCHK(fr_ntt_twiddles(logM, pk->tw.w(), pk->twinv.w(), minv.w(), s));      // w^k and w^-k, k < M/2, and 1/M
   // the Q kernel slices of this rank and their spectra (with the 1/M of the inverse transform)
   hipLaunchKernelGGL(k_recip_blocks, dim3(grid_blocks(QM)), dim3(256), 0, s, (const uint32_t*)fact.w(), (const uint32_t*)invfact.w(), n, pk->qs0, pk->qcnt, Bi, Q, pk->ghat.w());
-  ZCHK(ntt_forward(pk->ghat.w(), logM, pk->tw.w(), nullptr, s, Q));
-  hipLaunchKernelGGL(k_scale_all, dim3(grid_blocks(QM)), dim3(256), 0, s, pk->ghat.w(), (const uint32_t*)(consts.w() + K_NINV * FW), QM);
+  ZCHK(fr_ntt_forward(pk->ghat.w(), logM, pk->tw.w(), nullptr, s, Q));
+  hipLaunchKernelGGL(k_scale_all, dim3(grid_blocks(QM)), dim3(256), 0, s, pk->ghat.w(), (const uint32_t*)minv.w(), QM);
 
   // ---- per-wire evaluations u_i(x) = sum_j A[j][i] L_j(x)  and the scalars of crs.rs:66-84 ----
   Dev ue, ve, we, y; ZCHK(ue.alloc(rows * FRB)); ZCHK(ve.alloc(rows * FRB)); ZCHK(we.alloc(rows * FRB)); ZCHK(y.alloc(rows * FRB));
@@ -614,9 +452,9 @@ static int prove_submit(zkt_groth16_pk* pk, int ps, const uint64_t* wires, bool 
     // a, b, c side by side (grid.y): 2 + 2 k launches for transforms of k passes instead of 3 (1 + 2 k)
     hipLaunchKernelGGL(k_prep_blocks, dim3(grid_blocks(QM), 3), dim3(256), 0, q, (const uint32_t*)pk->z_m[0].w(), (const uint32_t*)pk->z_m[1].w(), (const uint32_t*)pk->z_m[2].w(),
                        (const uint32_t*)pk->cinv.w(), n, pk->Bi, Q, pk->X.w());
-    ZCHK(ntt_forward(pk->X.w(), pk->logM, pk->tw.w(), pk->ghat.w(), q, Q, 3, QM));     // block spectrum * spectrum of its slice of 1/d (and 1/M)
+    ZCHK(fr_ntt_forward(pk->X.w(), pk->logM, pk->tw.w(), pk->ghat.w(), q, Q, 3, QM));     // block spectrum * spectrum of its slice of 1/d (and 1/M)
     if (Q > 1) hipLaunchKernelGGL(k_sum_blocks, dim3(grid_blocks(M), 3), dim3(256), 0, q, pk->X.w(), M, Q);
-    ZCHK(ntt_inverse(pk->X.w(), pk->logM, pk->twinv.w(), q, 1, 3, QM));
+    ZCHK(fr_ntt_inverse(pk->X.w(), pk->logM, pk->twinv.w(), q, 1, 3, QM));
     hipLaunchKernelGGL(k_hvals, dim3(grid_blocks(pk->qcnt)), dim3(256), 0, q, (const uint32_t*)pk->X.w(), QM, (const uint32_t*)pk->P.w(), pk->qs0, pk->qcnt, sC.w() + nC1 * FW);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(pk->e_q, q));

@@ -173,11 +173,5 @@ extern "C" int zkt_internal_jac_sum(int grp, const uint32_t* dev_partials, size_
 // zkt_shutdown: device memory held by the per-key caches of zkt_protocols.hip and zkt_pinocchio.hip
 extern "C" void zkt_internal_clear_caches();
 extern "C" void zkt_pinocchio_clear_caches();
-// zkt_groth16_r1cs.hip: its Fr transform, for zkt_poly.hip.  Device pointers to Montgomery elements of 8 words; they return a ZKT_* status.
-// forward: natural order in, bit-reversed spectrum out, times `mulvec` (same order) when given; inverse: the reverse, WITHOUT the 1/N; `batch` consecutive transforms
-int zkt_fr_ntt_forward(uint32_t* a, int logN, const uint32_t* tw, const uint32_t* mulvec, hipStream_t s, size_t batch);
-int zkt_fr_ntt_inverse(uint32_t* a, int logN, const uint32_t* twinv, hipStream_t s, size_t batch);
-int zkt_fr_ntt_twiddles(int logN, uint32_t* tw, uint32_t* twinv, uint32_t* ninv, hipStream_t s);      // N/2 powers each way and 1/N; allocates and waits for s
-int zkt_fr_scan_mul(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);                      // inclusive prefix product; allocates and waits for s
 // zkt_shutdown: the twiddle tables of zkt_poly.hip
 extern "C" void zkt_poly_clear_caches();

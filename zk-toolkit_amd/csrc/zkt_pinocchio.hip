@@ -10,21 +10,13 @@
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
-#include "abi.h"
+#include "fr_vec.h"
 #include "zkt_internal.h"
 #include "../../include/zkt.h"
 #include "host_abi.h"
 
 namespace zkt {
 typedef FrC C;
-// out[i] = P_i(x) for `rows` dense polynomials of n coefficients, Montgomery (Polynomial::eval_at, polynomial.rs:240-249)
-__global__ void __launch_bounds__(64) k_pin_poly_eval(const uint32_t* __restrict__ P, size_t rows, size_t n, const uint32_t* __restrict__ x, uint32_t* __restrict__ out_mont) {
-  size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-  if (i >= rows) return;
-  Fp<C> xm = ld_fp<C>(x), acc = fp_zero<C>();
-  for (size_t k = n; k-- > 0;) acc = fp_add(fp_mul(acc, xm), ld_fp<C>(P + (i * n + k) * 8));
-  st_raw<C>(out_mont + i * 8, acc);
-}
 // per wire i: the seven scalars of crs.rs:86-108,122-124 (canonical); rnd = r_v, r_w, alpha_v, alpha_w, alpha_y, beta, gamma, s
 //   col 0 r_v v_i   1 r_w w_i   2 r_y y_i   3 r_v alpha_v v_i   4 r_w alpha_w w_i   5 r_y alpha_y y_i   6 beta (r_v v_i + r_w w_i + r_y y_i)
 // thread 0 also writes the single scalars of crs.rs:110-140: 1, alpha_v, alpha_w, alpha_y, gamma, gamma beta, T = r_y t(s), T alpha_v, T alpha_y, T beta
@@ -40,9 +32,8 @@ __global__ void __launch_bounds__(64) k_pin_scalars(const uint32_t* __restrict__
     st_fp<C>(cols + (6 * rows + i) * 8, fp_mul(beta, fp_add(fp_add(v, w), y)));
   }
   if (i == 0) {
-    Fp<C> gamma = ld_fp<C>(rnd + 48), s = ld_fp<C>(rnd + 56), one = fp_one<C>(), t = one, ii = fp_zero<C>();
-    for (size_t k = 1; k <= n; ++k) { ii = fp_add(ii, one); t = fp_mul(t, fp_sub(s, ii)); }     // QAP::build_t(f,n).eval_at(s), qap.rs:115-135
-    Fp<C> T = fp_mul(r_y, t);
+    Fp<C> gamma = ld_fp<C>(rnd + 48), s = ld_fp<C>(rnd + 56), one = fp_one<C>();
+    Fp<C> T = fp_mul(r_y, fr_t_at(s, n));
     st_fp<C>(singles, one); st_fp<C>(singles + 8, a_v); st_fp<C>(singles + 16, a_w); st_fp<C>(singles + 24, a_y); st_fp<C>(singles + 32, gamma);
     st_fp<C>(singles + 40, fp_mul(gamma, beta)); st_fp<C>(singles + 48, T); st_fp<C>(singles + 56, fp_mul(T, a_v)); st_fp<C>(singles + 64, fp_mul(T, a_y));
     st_fp<C>(singles + 72, fp_mul(T, beta));
@@ -217,7 +208,7 @@ int zkt_pinocchio_setup(zkt_pinocchio_crs* c, const uint64_t* vi, const uint64_t
   const uint64_t* polys[3] = {vi, wi, yi}; Dev* ev[3] = {&dve, &dwe, &dye};
   for (int k = 0; k < 3; ++k) {
     ZCHK(up(dP, polys[k], rows * n * FRB, s));
-    hipLaunchKernelGGL(k_pin_poly_eval, dim3(grid_blocks(rows, 64)), dim3(64), 0, s, (const uint32_t*)dP.w(), rows, n, (const uint32_t*)(drnd.w() + 56), ev[k]->w());
+    fr_eval_rows(dP.w(), rows, n, drnd.w() + 56, ev[k]->w(), s);
   }
   hipLaunchKernelGGL(k_pin_scalars, dim3(grid_blocks(rows, 64)), dim3(64), 0, s, (const uint32_t*)dve.w(), (const uint32_t*)dwe.w(), (const uint32_t*)dye.w(),
                      (const uint32_t*)drnd.w(), n, rows, dcols.w(), dsing.w());

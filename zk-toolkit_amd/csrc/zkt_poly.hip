@@ -4,7 +4,7 @@
 // The reference multiplies schoolbook and divides by long division, O(n^2) field operations.  Quotient and remainder are unique, and Fr has 2-adicity 32, so
 // the same coefficients come out of exact NTT arithmetic:
 //   product     min(na, nb) <= POLY_DIRECT_MAX: one lane per output coefficient over the shorter operand (k_mul_direct).  Otherwise both operands are
-//               transformed at N = 2^ceil(log2(na + nb - 1)) by the LDS-fused transform of zkt_groth16_r1cs.hip, the pointwise product rides on the last
+//               transformed at N = 2^ceil(log2(na + nb - 1)) by the LDS-fused transform of zkt_fr_vec.hip, the pointwise product rides on the last
 //               launch of the second forward transform (its `mulvec`), and the 1/N rides on the pass that stores the result.  a == b shares one transform.
 //   division    L = na - nb + 1 quotient coefficients.  rev(q) = rev(a) / rev(b) mod x^L is a power series quotient.  L <= POLY_DIV_DIRECT_MAX: one block
 //               runs the triangular recurrence (k_div_direct).  Otherwise g = 1 / rev(b) by Newton steps p -> 2p from g = 1 / b_lead: with f g = 1 + x^p e
@@ -23,7 +23,7 @@
 #include <vector>
 #include <mutex>
 #include <cstring>
-#include "abi.h"
+#include "fr_vec.h"
 #include "zkt_internal.h"
 #include "../../include/zkt.h"
 #include "host_abi.h"
@@ -31,8 +31,6 @@
 namespace zkt {
 namespace {
 typedef FrC C;
-typedef Fp<FrC> Fr;
-constexpr int FW = 8;                 // u32 words of an Fr element
 
 #ifdef ZKT_POLY_TIMING_DIRECT         // scratch libraries of tools/diag/poly_timing.py only (one path forced); the shipped library has no switch
 static constexpr size_t POLY_DIRECT_MAX = ZKT_POLY_TIMING_DIRECT;
@@ -47,29 +45,6 @@ static constexpr size_t EVAL_SPLIT_MIN_N = 2 * (size_t)EVAL_CHUNK;      // the s
 static constexpr size_t EVAL_SPLIT_MAX_K = 1024;                        // ... and below this many points (above it the points alone fill the device)
 static_assert(((size_t)1 << POLY_MAX_LOG) == ZKT_POLY_MAX_LEN, "twiddle cache covers every transform size");
 
-// 128-bit moves, as k_ntt_group does
-__device__ inline Fr ldm(const uint32_t* p) {
-  const uint4* s = reinterpret_cast<const uint4*>(p); const uint4 a = s[0], b = s[1]; Fr r;
-  r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w; r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w; return r;
-}
-__device__ inline void stm(uint32_t* p, const Fr& a) {
-  uint4* d = reinterpret_cast<uint4*>(p);
-  d[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]); d[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
-// the integer x as the Montgomery value x R (what fp_from_words does to canonical words)
-__device__ inline Fr to_mont(const Fr& x) { uint32_t w[FW];
-#pragma unroll
-  for (int i = 0; i < FW; ++i) w[i] = x.v[i];
-  return fp_from_words<C>(w); }
-__device__ inline Fr from_mont(const Fr& x) { uint32_t w[FW]; fp_to_words(x, w); Fr r;
-#pragma unroll
-  for (int i = 0; i < FW; ++i) r.v[i] = w[i];
-  return r; }
-// CANON: the caller's layout (any 256-bit integer on load, the canonical residue on store); otherwise Montgomery
-template <bool CANON> __device__ inline Fr ldx(const uint32_t* p) { Fr x = ldm(p); return CANON ? to_mont(x) : x; }
-template <bool CANON> __device__ inline void stx(uint32_t* p, const Fr& a) { stm(p, CANON ? from_mont(a) : a); }
-__device__ inline Fr fr_small(uint32_t k) { uint32_t w[8] = {k, 0, 0, 0, 0, 0, 0, 0}; return fp_from_words<C>(w); }
-
 // dst[i] = src[start + step * i] (* *scale) for i < cnt, zero for cnt <= i < n: load, store, reversal, zero padding and the 1/N of a transform in one pass
 template <bool IN_CANON, bool OUT_CANON>
 __global__ void __launch_bounds__(256) k_gather(uint32_t* __restrict__ dst, size_t n, const uint32_t* __restrict__ src, size_t cnt, long long start, int step,
@@ -78,7 +53,7 @@ __global__ void __launch_bounds__(256) k_gather(uint32_t* __restrict__ dst, size
   Fr v = fp_zero<C>();
   if (i < cnt) {
     v = ldx<IN_CANON>(src + (size_t)(start + (long long)step * (long long)i) * FW);
-    if (scale) { Fr s = ldm(scale); if (scale_sq) s = fp_sqr(s); v = fp_mul(v, s); }
+    if (scale) { Fr s = ldm4(scale); if (scale_sq) s = fp_sqr(s); v = fp_mul(v, s); }
   }
   stx<OUT_CANON>(dst + i * FW, v);
 }
@@ -90,69 +65,69 @@ __global__ void __launch_bounds__(256) k_mul_direct(const uint32_t* __restrict__
   const size_t j0 = k + 1 > nl ? k + 1 - nl : 0, j1 = k < ns - 1 ? k : ns - 1;
   Fr acc = fp_zero<C>();
   for (size_t j = j0; j <= j1; ++j) {
-    Fr a = ldm(sh + j * FW), b = ldm(lg + (k - j) * FW);
+    Fr a = ldm4(sh + j * FW), b = ldm4(lg + (k - j) * FW);
     if (CANON) { a = fp_canon32(a); b = fp_canon32(b); }
     acc = fp_add(acc, fp_mul(a, b));
   }
-  stm(out + k * FW, CANON ? to_mont(acc) : acc);
+  stm4(out + k * FW, CANON ? to_mont(acc) : acc);
 }
 __global__ void __launch_bounds__(256) k_sqr_all(uint32_t* __restrict__ a, size_t n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= n) return;
-  stm(a + i * FW, fp_sqr(ldm(a + i * FW)));
+  stm4(a + i * FW, fp_sqr(ldm4(a + i * FW)));
 }
 // out[i] = a[i] - b[i] (* *scale on b), i < n; out may be a
 template <bool OUT_CANON>
 __global__ void __launch_bounds__(256) k_sub(uint32_t* out, const uint32_t* a, const uint32_t* __restrict__ b, size_t n, const uint32_t* __restrict__ scale) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= n) return;
-  Fr v = ldm(b + i * FW); if (scale) v = fp_mul(v, ldm(scale));
-  stx<OUT_CANON>(out + i * FW, fp_sub(ldm(a + i * FW), v));
+  Fr v = ldm4(b + i * FW); if (scale) v = fp_mul(v, ldm4(scale));
+  stx<OUT_CANON>(out + i * FW, fp_sub(ldm4(a + i * FW), v));
 }
 // dst[i] += a[i] + b[i], i < n
 __global__ void __launch_bounds__(256) k_add2(uint32_t* __restrict__ dst, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, size_t n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= n) return;
-  stm(dst + i * FW, fp_add(ldm(dst + i * FW), fp_add(ldm(a + i * FW), ldm(b + i * FW))));
+  stm4(dst + i * FW, fp_add(ldm4(dst + i * FW), fp_add(ldm4(a + i * FW), ldm4(b + i * FW))));
 }
 // *out = 1 / *in (one lane); a zero is reported through err
 __global__ void k_inv1(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, unsigned long long* err, unsigned long long index) {
   if (threadIdx.x || blockIdx.x) return;
-  const Fr v = ldm(in);
-  if (fp_is_zero(v)) { atomicMin(err, index); stm(out, v); return; }
-  stm(out, fp_inv(v));
+  const Fr v = ldm4(in);
+  if (fp_is_zero(v)) { atomicMin(err, index); stm4(out, v); return; }
+  stm4(out, fp_inv(v));
 }
 // Power series quotient by the triangular recurrence, one block: with ra = rev(a), f = rev(b) and rq = rev(q),
 // rq[k] = (ra[k] - sum_{1 <= j <= k} f[j] rq[k - j]) / f[0].  q[L-1-k] carries the running value of rq[k]; step k fixes it and subtracts its multiples from the later ones.
 __global__ void __launch_bounds__(256) k_div_direct(const uint32_t* __restrict__ a, size_t na, const uint32_t* __restrict__ b, size_t nb, uint32_t* q, size_t L,
                                                     const uint32_t* __restrict__ finv) {
   const size_t t = threadIdx.x;
-  for (size_t k = t; k < L; k += 256) stm(q + (L - 1 - k) * FW, ldm(a + (na - 1 - k) * FW));
+  for (size_t k = t; k < L; k += 256) stm4(q + (L - 1 - k) * FW, ldm4(a + (na - 1 - k) * FW));
   __syncthreads();
-  const Fr fi = ldm(finv);
+  const Fr fi = ldm4(finv);
   for (size_t k = 0; k < L; ++k) {
-    const Fr v = fp_mul(ldm(q + (L - 1 - k) * FW), fi);
+    const Fr v = fp_mul(ldm4(q + (L - 1 - k) * FW), fi);
     __syncthreads();
-    if (t == 0) stm(q + (L - 1 - k) * FW, v);
+    if (t == 0) stm4(q + (L - 1 - k) * FW, v);
     for (size_t i = k + 1 + t; i < L && i - k < nb; i += 256)
-      stm(q + (L - 1 - i) * FW, fp_sub(ldm(q + (L - 1 - i) * FW), fp_mul(ldm(b + (nb - 1 - (i - k)) * FW), v)));
+      stm4(q + (L - 1 - i) * FW, fp_sub(ldm4(q + (L - 1 - i) * FW), fp_mul(ldm4(b + (nb - 1 - (i - k)) * FW), v)));
     __syncthreads();
   }
 }
 // Newton update: g[p + i] = -E[i] / N^2, i < cnt (E carries the N of two unscaled inverse transforms)
 __global__ void __launch_bounds__(256) k_newton_update(uint32_t* __restrict__ g_hi, const uint32_t* __restrict__ E, size_t cnt, const uint32_t* __restrict__ ninv) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= cnt) return;
-  const Fr s = fp_sqr(ldm(ninv));
-  stm(g_hi + i * FW, fp_neg(fp_mul(ldm(E + i * FW), s)));
+  const Fr s = fp_sqr(ldm4(ninv));
+  stm4(g_hi + i * FW, fp_neg(fp_mul(ldm4(E + i * FW), s)));
 }
 // dst[i] = sum of src[j] over j = i mod N, j < n: the polynomial modulo x^N - 1
 __global__ void __launch_bounds__(256) k_fold(uint32_t* __restrict__ dst, size_t N, const uint32_t* __restrict__ src, size_t n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= N) return;
   Fr acc = fp_zero<C>();
-  for (size_t j = i; j < n; j += N) acc = fp_add(acc, ldm(src + j * FW));
-  stm(dst + i * FW, acc);
+  for (size_t j = i; j < n; j += N) acc = fp_add(acc, ldm4(src + j * FW));
+  stm4(dst + i * FW, acc);
 }
 // *top = max(*top, i + 1) over the non-zero a[i]
 __global__ void __launch_bounds__(256) k_top_nonzero(const uint32_t* __restrict__ a, size_t n, unsigned long long* top) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= n) return;
-  if (!fp_is_zero(ldm(a + i * FW))) atomicMax(top, (unsigned long long)(i + 1));
+  if (!fp_is_zero(ldm4(a + i * FW))) atomicMax(top, (unsigned long long)(i + 1));
 }
 
 // ---- product tree of t = prod_{i=1..n} (x - i) ---------------------------------------------------------------------------
@@ -160,7 +135,7 @@ __global__ void __launch_bounds__(256) k_top_nonzero(const uint32_t* __restrict_
 __device__ inline size_t tree_deg(size_t n, size_t s, size_t j) { const size_t lo = j * s; return lo >= n ? 0 : (n - lo < s ? n - lo : s); }
 __global__ void __launch_bounds__(256) k_tree_leaves(uint32_t* __restrict__ out, size_t n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= n) return;
-  stm(out + 2 * i * FW, fp_neg(fr_small((uint32_t)(i + 1)))); stm(out + (2 * i + 1) * FW, fp_one<C>());
+  stm4(out + 2 * i * FW, fp_neg(fr_small((uint32_t)(i + 1)))); stm4(out + (2 * i + 1) * FW, fp_one<C>());
 }
 // one lane per (node, coefficient) of the level of span 2s
 __global__ void __launch_bounds__(256) k_tree_direct(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, size_t s, size_t n, size_t nodes) {
@@ -168,21 +143,21 @@ __global__ void __launch_bounds__(256) k_tree_direct(const uint32_t* __restrict_
   const size_t j = i / per, k = i % per, dl = tree_deg(n, s, 2 * j), dr = tree_deg(n, s, 2 * j + 1);
   const uint32_t* l = src + (2 * j) * (s + 1) * FW; const uint32_t* r = src + (2 * j + 1) * (s + 1) * FW;
   Fr acc = fp_zero<C>();
-  if (dr == 0) { if (k <= dl) acc = ldm(l + k * FW); }               // an only child (the right one would be the constant 1)
+  if (dr == 0) { if (k <= dl) acc = ldm4(l + k * FW); }               // an only child (the right one would be the constant 1)
   else if (k <= dl + dr) {
     const size_t i0 = k > dr ? k - dr : 0, i1 = k < dl ? k : dl;
-    for (size_t a = i0; a <= i1; ++a) acc = fp_add(acc, fp_mul(ldm(l + a * FW), ldm(r + (k - a) * FW)));
+    for (size_t a = i0; a <= i1; ++a) acc = fp_add(acc, fp_mul(ldm4(l + a * FW), ldm4(r + (k - a) * FW)));
   }
-  stm(dst + i * FW, acc);
+  stm4(dst + i * FW, acc);
 }
 // X[j] = left child of node j, Y[j] = right child (or the constant 1), each zero-padded to N = 2s
 __global__ void __launch_bounds__(256) k_tree_gather(const uint32_t* __restrict__ src, uint32_t* __restrict__ X, uint32_t* __restrict__ Y, size_t s, size_t n, size_t nodes) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, N = 2 * s; if (i >= nodes * N) return;
   const size_t j = i / N, k = i % N, dl = tree_deg(n, s, 2 * j), dr = tree_deg(n, s, 2 * j + 1);
-  stm(X + i * FW, k <= dl ? ldm(src + ((2 * j) * (s + 1) + k) * FW) : fp_zero<C>());
+  stm4(X + i * FW, k <= dl ? ldm4(src + ((2 * j) * (s + 1) + k) * FW) : fp_zero<C>());
   Fr y = fp_zero<C>();
-  if (dr == 0) { if (k == 0) y = fp_one<C>(); } else if (k <= dr) y = ldm(src + ((2 * j + 1) * (s + 1) + k) * FW);
-  stm(Y + i * FW, y);
+  if (dr == 0) { if (k == 0) y = fp_one<C>(); } else if (k <= dr) y = ldm4(src + ((2 * j + 1) * (s + 1) + k) * FW);
+  stm4(Y + i * FW, y);
 }
 // the cyclic products X (times N) -> the level of span 2s: the leading 1 is written, and taken off coefficient 0 where it wrapped (two full children)
 __global__ void __launch_bounds__(256) k_tree_scatter(const uint32_t* __restrict__ X, uint32_t* __restrict__ dst, size_t s, size_t n, size_t nodes, const uint32_t* __restrict__ ninv) {
@@ -190,8 +165,8 @@ __global__ void __launch_bounds__(256) k_tree_scatter(const uint32_t* __restrict
   const size_t j = i / per, k = i % per, d = tree_deg(n, s, 2 * j) + tree_deg(n, s, 2 * j + 1);
   Fr v = fp_zero<C>();
   if (k == d) v = fp_one<C>();
-  else if (k < d) { v = fp_mul(ldm(X + (j * N + k) * FW), ldm(ninv)); if (k == 0 && d == N) v = fp_sub(v, fp_one<C>()); }
-  stm(dst + i * FW, v);
+  else if (k < d) { v = fp_mul(ldm4(X + (j * N + k) * FW), ldm4(ninv)); if (k == 0 && d == N) v = fp_sub(v, fp_one<C>()); }
+  stm4(dst + i * FW, v);
 }
 
 // ---- evaluation ----------------------------------------------------------------------------------------------------
@@ -199,8 +174,8 @@ __global__ void __launch_bounds__(256) k_tree_scatter(const uint32_t* __restrict
 __global__ void __launch_bounds__(256) k_eval_horner(const uint32_t* __restrict__ coef, size_t n, const uint32_t* __restrict__ xs, size_t k, uint32_t* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; if (i >= k) return;
   const Fr x = ldx<true>(xs + i * FW);
-  Fr acc = ldm(coef + (n - 1) * FW);
-  for (size_t j = n - 1; j-- > 0;) acc = fp_add(fp_mul(acc, x), ldm(coef + j * FW));
+  Fr acc = ldm4(coef + (n - 1) * FW);
+  for (size_t j = n - 1; j-- > 0;) acc = fp_add(fp_mul(acc, x), ldm4(coef + j * FW));
   stx<true>(out + i * FW, acc);
 }
 // block (c, point): sum_{e < EVAL_CHUNK} coef[c EVAL_CHUNK + e] x^e.  A lane runs Horner over its EVAL_ITEMS coefficients, then a tree over the lanes:
@@ -211,16 +186,16 @@ __global__ void __launch_bounds__(EVAL_TPB) k_eval_split(const uint32_t* __restr
   const Fr x = ldx<true>(xs + (size_t)blockIdx.y * FW);
   const size_t base = (size_t)blockIdx.x * EVAL_CHUNK + (size_t)t * EVAL_ITEMS;
   Fr acc = fp_zero<C>();
-  for (int e = EVAL_ITEMS - 1; e >= 0; --e) { acc = fp_mul(acc, x); if (base + e < n) acc = fp_add(acc, ldm(coef + (base + e) * FW)); }
+  for (int e = EVAL_ITEMS - 1; e >= 0; --e) { acc = fp_mul(acc, x); if (base + e < n) acc = fp_add(acc, ldm4(coef + (base + e) * FW)); }
   Fr xp = x;
   for (int e = 1; e < EVAL_ITEMS; e <<= 1) xp = fp_sqr(xp);                 // x^EVAL_ITEMS
-  stm(lds + t * FW, acc); __syncthreads();
+  stm4(lds + t * FW, acc); __syncthreads();
   for (int d = 1; d < EVAL_TPB; d <<= 1) {
-    if ((t & (2 * d - 1)) == 0) { acc = fp_add(acc, fp_mul(ldm(lds + (t + d) * FW), xp)); stm(lds + t * FW, acc); }
+    if ((t & (2 * d - 1)) == 0) { acc = fp_add(acc, fp_mul(ldm4(lds + (t + d) * FW), xp)); stm4(lds + t * FW, acc); }
     xp = fp_sqr(xp);
     __syncthreads();
   }
-  if (t == 0) stm(part + ((size_t)blockIdx.y * chunks + blockIdx.x) * FW, acc);
+  if (t == 0) stm4(part + ((size_t)blockIdx.y * chunks + blockIdx.x) * FW, acc);
 }
 // one lane per point: Horner over its blocks in y = x^EVAL_CHUNK
 __global__ void __launch_bounds__(256) k_eval_combine(const uint32_t* __restrict__ part, size_t chunks, const uint32_t* __restrict__ xs, size_t k, uint32_t* __restrict__ out) {
@@ -228,8 +203,8 @@ __global__ void __launch_bounds__(256) k_eval_combine(const uint32_t* __restrict
   Fr y = ldx<true>(xs + i * FW);
   for (int e = 1; e < EVAL_CHUNK; e <<= 1) y = fp_sqr(y);
   const uint32_t* p = part + i * chunks * FW;
-  Fr acc = ldm(p + (chunks - 1) * FW);
-  for (size_t j = chunks - 1; j-- > 0;) acc = fp_add(fp_mul(acc, y), ldm(p + j * FW));
+  Fr acc = ldm4(p + (chunks - 1) * FW);
+  for (size_t j = chunks - 1; j-- > 0;) acc = fp_add(fp_mul(acc, y), ldm4(p + j * FW));
   stx<true>(out + i * FW, acc);
 }
 // out[p][j] = sum_i wires[i] M_p[i][j], p = blockIdx.y over the three rows x n coefficient arrays (caller's layout in, Montgomery out)
@@ -239,7 +214,7 @@ __global__ void __launch_bounds__(256) k_wire_comb(Comb3 c, const uint32_t* __re
   const uint32_t* m = c.m[blockIdx.y];
   Fr acc = fp_zero<C>();
   for (size_t i = 0; i < rows; ++i) acc = fp_add(acc, fp_mul(ldx<true>(wires + i * FW), ldx<true>(m + (i * n + j) * FW)));
-  stm(c.out[blockIdx.y] + j * FW, acc);
+  stm4(c.out[blockIdx.y] + j * FW, acc);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -270,7 +245,7 @@ int tw_get(int logN, Tw& out) {
     void* p = nullptr;
     if (hipMalloc(&p, (2 * half + 1) * FRB) != hipSuccess) { (void)hipGetLastError(); return ZKT_ERR_DEVICE; }
     uint32_t* w = (uint32_t*)p;
-    const int rc = zkt_fr_ntt_twiddles(logN, w, w + half * FW, w + 2 * half * FW, nullptr);
+    const int rc = fr_ntt_twiddles(logN, w, w + half * FW, w + 2 * half * FW, nullptr);
     if (rc != ZKT_OK) { (void)hipFree(p); return rc; }
     e.tw = w; e.twinv = w + half * FW; e.ninv = w + 2 * half * FW;
   }
@@ -298,15 +273,15 @@ int pmul(Pool& pool, const uint32_t* a, size_t na, const uint32_t* b, size_t nb,
   PGET(A, pool, N);
   gather<CANON, false>(A, N, a, na, 0, 1, nullptr, 0, s);
   if (a == b && na == nb) {
-    ZCHK(zkt_fr_ntt_forward(A, logN, tw.tw, nullptr, s, 1));
+    ZCHK(fr_ntt_forward(A, logN, tw.tw, nullptr, s, 1));
     hipLaunchKernelGGL(k_sqr_all, dim3(grid_blocks(N)), dim3(256), 0, s, A, N);
   } else {
     PGET(B, pool, N);
     gather<CANON, false>(B, N, b, nb, 0, 1, nullptr, 0, s);
-    ZCHK(zkt_fr_ntt_forward(B, logN, tw.tw, nullptr, s, 1));
-    ZCHK(zkt_fr_ntt_forward(A, logN, tw.tw, B, s, 1));
+    ZCHK(fr_ntt_forward(B, logN, tw.tw, nullptr, s, 1));
+    ZCHK(fr_ntt_forward(A, logN, tw.tw, B, s, 1));
   }
-  ZCHK(zkt_fr_ntt_inverse(A, logN, tw.twinv, s, 1));
+  ZCHK(fr_ntt_inverse(A, logN, tw.twinv, s, 1));
   gather<false, CANON>(out, keep, A, keep, 0, 1, tw.ninv, 0, s);
   HIPCHK(hipGetLastError()); return ZKT_OK;
 }
@@ -322,12 +297,12 @@ int newton_inverse(Pool& pool, const uint32_t* b, size_t nb, uint32_t* g, size_t
     Tw tw; ZCHK(tw_get(logN, tw));
     gather<false, false>(T, N, b, nb < N ? nb : N, (long long)nb - 1, -1, nullptr, 0, s);        // rev(b) mod x^N
     gather<false, false>(GS, N, g, p, 0, 1, nullptr, 0, s);
-    ZCHK(zkt_fr_ntt_forward(GS, logN, tw.tw, nullptr, s, 1));
-    ZCHK(zkt_fr_ntt_forward(T, logN, tw.tw, GS, s, 1));
-    ZCHK(zkt_fr_ntt_inverse(T, logN, tw.twinv, s, 1));                                         // N (f g mod x^N - 1): coefficients p .. N-1 are N e
+    ZCHK(fr_ntt_forward(GS, logN, tw.tw, nullptr, s, 1));
+    ZCHK(fr_ntt_forward(T, logN, tw.tw, GS, s, 1));
+    ZCHK(fr_ntt_inverse(T, logN, tw.twinv, s, 1));                                         // N (f g mod x^N - 1): coefficients p .. N-1 are N e
     gather<false, false>(E, N, T + p * FW, p, 0, 1, nullptr, 0, s);
-    ZCHK(zkt_fr_ntt_forward(E, logN, tw.tw, GS, s, 1));
-    ZCHK(zkt_fr_ntt_inverse(E, logN, tw.twinv, s, 1));                                         // N^2 (e g)
+    ZCHK(fr_ntt_forward(E, logN, tw.tw, GS, s, 1));
+    ZCHK(fr_ntt_inverse(E, logN, tw.twinv, s, 1));                                         // N^2 (e g)
     hipLaunchKernelGGL(k_newton_update, dim3(grid_blocks(p)), dim3(256), 0, s, g + p * FW, (const uint32_t*)E, p, (const uint32_t*)tw.ninv);
   }
   HIPCHK(hipGetLastError()); return ZKT_OK;
@@ -372,9 +347,9 @@ int divrem_dev(Pool& pool, const uint32_t* a, size_t na, const uint32_t* b, size
     hipLaunchKernelGGL(k_fold, dim3(grid_blocks(N)), dim3(256), 0, s, QF, N, (const uint32_t*)q, L);
     hipLaunchKernelGGL(k_fold, dim3(grid_blocks(N)), dim3(256), 0, s, BF, N, b, nb);
     hipLaunchKernelGGL(k_fold, dim3(grid_blocks(N)), dim3(256), 0, s, AF, N, a, na);
-    ZCHK(zkt_fr_ntt_forward(BF, logN, tw.tw, nullptr, s, 1));
-    ZCHK(zkt_fr_ntt_forward(QF, logN, tw.tw, BF, s, 1));
-    ZCHK(zkt_fr_ntt_inverse(QF, logN, tw.twinv, s, 1));
+    ZCHK(fr_ntt_forward(BF, logN, tw.tw, nullptr, s, 1));
+    ZCHK(fr_ntt_forward(QF, logN, tw.tw, BF, s, 1));
+    ZCHK(fr_ntt_inverse(QF, logN, tw.twinv, s, 1));
     hipLaunchKernelGGL(k_sub<false>, dim3(grid_blocks(nr)), dim3(256), 0, s, rem, (const uint32_t*)AF, (const uint32_t*)QF, nr, (const uint32_t*)tw.ninv);
   }
   HIPCHK(hipGetLastError()); return ZKT_OK;
@@ -399,9 +374,9 @@ int build_t_dev(Pool& pool, size_t n, uint32_t* out) {
       Tw tw; ZCHK(tw_get(logN, tw));
       if (!X) { const size_t cap = 2 * n + 2 * POLY_DIRECT_MAX + 4; X = pool.get(cap); Y = pool.get(cap); if (!X || !Y) return ZKT_ERR_DEVICE; }     // nodes * N < n + 2 sp <= 2n at every level
       hipLaunchKernelGGL(k_tree_gather, dim3(grid_blocks(nodes * N)), dim3(256), 0, s, (const uint32_t*)cur, X, Y, sp, n, nodes);
-      ZCHK(zkt_fr_ntt_forward(Y, logN, tw.tw, nullptr, s, nodes));
-      ZCHK(zkt_fr_ntt_forward(X, logN, tw.tw, Y, s, nodes));
-      ZCHK(zkt_fr_ntt_inverse(X, logN, tw.twinv, s, nodes));
+      ZCHK(fr_ntt_forward(Y, logN, tw.tw, nullptr, s, nodes));
+      ZCHK(fr_ntt_forward(X, logN, tw.tw, Y, s, nodes));
+      ZCHK(fr_ntt_inverse(X, logN, tw.twinv, s, nodes));
       hipLaunchKernelGGL(k_tree_scatter, dim3(grid_blocks(nodes * per)), dim3(256), 0, s, (const uint32_t*)X, nxt, sp, n, nodes, (const uint32_t*)tw.ninv);
     }
     uint32_t* t = cur; cur = nxt; nxt = t;

@@ -9,7 +9,7 @@
 #include <cstring>
 #include <cstdio>
 #include <memory>
-#include "abi.h"
+#include "fr_vec.h"
 #include "zkt_internal.h"
 #include "../../include/zkt.h"
 #include "host_abi.h"
@@ -26,15 +26,6 @@ __global__ void __launch_bounds__(256) k_lincomb(const uint32_t* __restrict__ P,
   for (size_t i = 0; i < rows; ++i) acc = fp_add(acc, fp_mul(ld_fp<C>(a + i * C::N), ld_raw<C>(P + (i * n + k) * C::N)));   // aR * p * R^-1 = a p
   st_raw<C>(out + k * C::N, acc);
 }
-// out[i] = P_i(x) for `rows` dense polynomials of n coefficients (Polynomial::eval_at, polynomial.rs:240-249)
-template <class C>
-__global__ void __launch_bounds__(64) k_poly_eval(const uint32_t* __restrict__ P, size_t rows, size_t n, const uint32_t* __restrict__ x, uint32_t* __restrict__ out_mont) {
-  size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-  if (i >= rows) return;
-  Fp<C> xm = ld_fp<C>(x), acc = fp_zero<C>();
-  for (size_t k = n; k-- > 0;) acc = fp_add(fp_mul(acc, xm), ld_fp<C>(P + (i * n + k) * C::N));     // Horner, Montgomery domain
-  st_raw<C>(out_mont + i * C::N, acc);
-}
 // CRS::new scalar stage (crs.rs:59-116): y_i = (beta u_i(x) + alpha v_i(x) + w_i(x)) / (gamma | delta), x^k, x^k t(x)/delta
 __global__ void k_groth16_setup_scalars(const uint32_t* __restrict__ ue, const uint32_t* __restrict__ ve, const uint32_t* __restrict__ we,
                                         const uint32_t* __restrict__ trap /*alpha,beta,gamma,delta,x canonical*/, size_t n, size_t l, size_t m,
@@ -47,9 +38,7 @@ __global__ void k_groth16_setup_scalars(const uint32_t* __restrict__ ue, const u
     Fp<C> s = fp_add(fp_add(fp_mul(beta, ld_raw<C>(ue + i * 8)), fp_mul(alpha, ld_raw<C>(ve + i * 8))), fp_canon32(ld_raw<C>(we + i * 8)));   // products reduce any 256-bit operand; the bare addend is reduced explicitly
     st_fp<C>(y + i * 8, fp_mul(s, i <= l ? ginv : dinv));
   }
-  Fp<C> t = fp_one<C>(), one = fp_one<C>(), ii = fp_zero<C>();
-  for (size_t i = 1; i <= n; ++i) { ii = fp_add(ii, one); t = fp_mul(t, fp_sub(x, ii)); }       // QAP::build_t(f,n).eval_at(x), qap.rs:115-135
-  Fp<C> td = fp_mul(t, dinv), xp = one;
+  Fp<C> td = fp_mul(fr_t_at(x, n), dinv), xp = fp_one<C>();
   for (size_t k = 0; k < n; ++k) { st_fp<C>(xpow + k * 8, xp); st_fp<C>(xt + k * 8, fp_mul(xp, td)); xp = fp_mul(xp, x); }
 }
 // r*s etc. are group-side in the reference (delta*r*s = two scalar muls), nothing to do here.
@@ -503,7 +492,7 @@ int zkt_groth16_setup(zkt_groth16_crs* c, const uint64_t* ui, const uint64_t* vi
   const uint64_t* polys[3] = {ui, vi, wi}; Dev* evals[3] = {&due, &dve, &dwe};
   for (int k = 0; k < 3; ++k) {
     if ((rc = up(dP, polys[k], rows * n * FRB, s))) return rc;
-    hipLaunchKernelGGL(k_poly_eval<FrC>, dim3(grid_blocks(rows, 64)), dim3(64), 0, s, (const uint32_t*)dP.w(), rows, n, (const uint32_t*)(dtrap.w() + 32), evals[k]->w());
+    fr_eval_rows(dP.w(), rows, n, dtrap.w() + 32, evals[k]->w(), s);
   }
   hipLaunchKernelGGL(k_groth16_setup_scalars, dim3(1), dim3(64), 0, s, (const uint32_t*)due.w(), (const uint32_t*)dve.w(), (const uint32_t*)dwe.w(),
                      (const uint32_t*)dtrap.w(), n, l, m, dy.w(), dxp.w(), dxt.w());
