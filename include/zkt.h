@@ -220,7 +220,9 @@ int zkt_gt_eq(const uint64_t* a_fq12, const uint64_t* b_fq12);
  * Verifier::verify verifier.rs:30-54.  The reference samples alpha,beta,gamma,delta,x (crs.rs:59-63) and r,s
  * (prover.rs:100-101) from OS entropy; here they are arguments (4-limb Fr, non-zero).  QAP polynomials ui/vi/wi are
  * (m+1) x n dense Fr coefficient arrays, low degree first (Prover.ui/vi/wi prover.rs:44-46); wires = a_0..a_m
- * (wires.rs:12-39), statement = a_0..a_l; h = quotient polynomial coefficients (prover.rs:64-71), h_len <= n. */
+ * (wires.rs:12-39), statement = a_0..a_l; h = quotient polynomial coefficients (prover.rs:64-71), h_len <= n.
+ * Every 4-limb value is reduced mod r on load; zkt_groth16_setup returns ZKT_ERR_INV_ZERO for a trapdoor that is 0 mod r (0, r or 2r; the
+ * reference's rand_elem(true) never draws one), checked on the host before anything is allocated or launched: the CRS is untouched. */
 typedef struct {
   size_t n, l, m;                       /* constraints, last statement wire, last wire (prover.rs:36-38) */
   zkt_g1_affine *g1_alpha, *g1_beta, *g1_delta, *g1_xi /*n*/, *g1_uvw_stmt /*l+1*/, *g1_uvw_wit /*m-l*/, *g1_xt_by_delta /*n*/;
@@ -306,7 +308,9 @@ int zkt_bls_verify_batch(const uint8_t* msgs, const uint64_t* offsets, const zkt
  * (n_io + n_mid) x n dense Fr coefficient arrays of Prover.vi/wi/yi (prover.rs:43-45), low degree first; wires 0..n_io-1 are
  * Witness::io() (witness.rs:20-23, the constant one included), the rest Witness::mid() (witness.rs:25-27); max_degree as
  * prover.rs:68-78.  rnd = r_v, r_w, alpha_v, alpha_w, alpha_y, beta, gamma, s (crs.rs:58-64,82), 4 limbs each, non-zero;
- * delta_v, delta_y = prover.rs:104-105; h = coefficients of p / t (prover.rs:143-146), h_len <= max_degree. */
+ * delta_v, delta_y = prover.rs:104-105; h = coefficients of p / t (prover.rs:143-146), h_len <= max_degree.
+ * Every 4-limb value is reduced mod r on load; zkt_pinocchio_setup returns ZKT_ERR_INV_ZERO for an rnd value that is 0 mod r (0, r or 2r),
+ * checked on the host before anything is allocated or launched: the CRS is untouched. */
 typedef struct {
   size_t n, n_io, n_mid, max_degree;
   zkt_g1_affine *vk_mid /*n_mid*/, *g1_wk_mid; zkt_g2_affine* g2_wk_mid; zkt_g1_affine *yk_mid, *alpha_vk_mid, *alpha_wk_mid, *alpha_yk_mid;

@@ -6,6 +6,8 @@
 // QAP polynomials arrive as dense coefficient arrays (low degree first), n coefficients each; the reference's
 // Polynomial trims trailing zeros, which only removes terms that contribute the point at infinity.
 #include "zkt_oracle.hpp"
+#include <future>
+#include <exception>
 using namespace zkto;
 
 namespace {
@@ -59,6 +61,7 @@ int zkto_groth16_setup(zkto_groth16_crs* c, const uint64_t* ui, const uint64_t* 
   const size_t n = c->n, l = c->l, m = c->m;
   G1Point g = g1_generator(); G2Point h = g2_generator();
   Fr alpha = ldr(alpha_), beta = ldr(beta_), gamma = ldr(gamma_), delta = ldr(delta_), x = ldr(x_);
+  for (const Fr* v : {&alpha, &beta, &gamma, &delta, &x}) if (v->is_zero()) return 1;       // rand_elem(true) draws no zero (crs.rs:59-63); ZKT_ERR_INV_ZERO, nothing written
   auto uvw_div = [&](size_t from, size_t to, const Fr& div, uint64_t* out) {     // calc_uvw_div! crs.rs:65-83
     for (size_t i = from; i <= to; ++i) {
       Fr u = beta * poly_eval(ui + i * n * FR, n, x);
@@ -154,6 +157,7 @@ int zkto_pinocchio_setup(zkto_pinocchio_crs* c, const uint64_t* vi, const uint64
   const size_t n = c->n, nio = c->n_io, nmid = c->n_mid;
   G1Point g1 = g1_generator(); G2Point g2 = g2_generator();
   Fr r_v = ldr(rnd), r_w = ldr(rnd + 4), alpha_v = ldr(rnd + 8), alpha_w = ldr(rnd + 12), alpha_y = ldr(rnd + 16), beta = ldr(rnd + 20), gamma = ldr(rnd + 24), s = ldr(rnd + 28);
+  for (const Fr* v : {&r_v, &r_w, &alpha_v, &alpha_w, &alpha_y, &beta, &gamma, &s}) if (v->is_zero()) return 1;   // rand_elem(true) (crs.rs:58-64,82); ZKT_ERR_INV_ZERO, nothing written
   Fr r_y = r_v * r_w;                                                                        // crs.rs:67
   G1Point g1_v = mul_fr(g1, r_v), g1_w = mul_fr(g1, r_w), g1_y = mul_fr(g1, r_y); G2Point g2_w = mul_fr(g2, r_w);   // :68-71
   for (size_t k = 0; k < nmid; ++k) {                                                        // :86-108, mid = mid_beg..=end
@@ -214,29 +218,37 @@ int zkto_pinocchio_prove(const zkto_pinocchio_crs* c, const uint64_t* wires, con
   return 0;
 }
 
-// Verifier::verify (verifier.rs:31-85): 1 accept, 0 reject, -2 if a tate() argument is the point at infinity (panic)
+// Verifier::verify (verifier.rs:31-85): 1 accept, 0 reject, -2 if a tate() argument is the point at infinity (panic).
+// The eleven pairings are independent, and one takes most of a second here: each runs on a thread of its own and is consumed in the reference's order, where a
+// panic of its tate() surfaces too (a rejection by an earlier check still wins over a panic of a later one).  The statement sums of :69-79 are formed while the
+// first pairings run; a panic inside them is kept until the reference would have reached it.
 int zkto_pinocchio_verify(const zkto_pinocchio_crs* c, const zkto_pinocchio_proof* pf, const uint64_t* io_wires) {
   init_fields();
   static Pairing pr;
-  auto e = [&](const G1Point& a, const G2Point& b) { return pr.tate(a, b); };
+  typedef std::shared_future<Fq12> Fut;
+  auto e = [&](const G1Point& a, const G2Point& b) -> Fut { return std::async(std::launch::async, [a, b] { return pr.tate(a, b); }).share(); };
   try {
     G1Point v_mid = ldg1(pf->v_mid_s), g1_w = ldg1(pf->g1_w_mid_s), y_mid = ldg1(pf->y_mid_s);
     G2Point g2_w = ldg2(pf->g2_w_mid_s), one2 = ldg2(c->one_g2);
-    {                                                                                        // :43-49
-      G1Point vwy = affine_add(affine_add(v_mid, g1_w), y_mid);
-      if (!(e(ldg1(pf->beta_vwy_mid_s), ldg2(c->gamma)) == e(vwy, ldg2(c->beta_gamma)))) return 0;
-    }
-    if (!(e(ldg1(pf->alpha_v_mid_s), one2) == e(v_mid, ldg2(c->alpha_v)))) return 0;         // :52-56
-    if (!(e(ldg1(pf->alpha_w_mid_s), one2) == e(ldg1(c->alpha_w), g2_w))) return 0;          // :57-61
-    if (!(e(ldg1(pf->alpha_y_mid_s), one2) == e(y_mid, ldg2(c->alpha_y)))) return 0;         // :62-66
-    G1Point v_s = v_mid, y_s = y_mid; G2Point w_s = g2_w;                                    // :69-79
-    for (size_t i = 0; i < c->n_io; ++i) {
-      Fr w = ldr(io_wires + i * FR);
-      v_s = affine_add(v_s, mul_fr(ldg1(c->vk_io + i * G1W), w));
-      w_s = affine_add(w_s, mul_fr(ldg2(c->wk_io + i * G2W), w));
-      y_s = affine_add(y_s, mul_fr(ldg1(c->yk_io + i * G1W), w));
-    }
-    Fq12 lhs = e(v_s, w_s), rhs = e(ldg1(c->t), ldg2(pf->h_s)) * e(y_s, one2);               // :81-84
+    G1Point vwy = affine_add(affine_add(v_mid, g1_w), y_mid);                                // :44
+    Fut four[8] = {e(ldg1(pf->beta_vwy_mid_s), ldg2(c->gamma)), e(vwy, ldg2(c->beta_gamma)),   // :43-49
+                   e(ldg1(pf->alpha_v_mid_s), one2), e(v_mid, ldg2(c->alpha_v)),              // :52-56
+                   e(ldg1(pf->alpha_w_mid_s), one2), e(ldg1(c->alpha_w), g2_w),               // :57-61
+                   e(ldg1(pf->alpha_y_mid_s), one2), e(y_mid, ldg2(c->alpha_y))};             // :62-66
+    Fut last[3]; std::exception_ptr late;
+    try {
+      G1Point v_s = v_mid, y_s = y_mid; G2Point w_s = g2_w;                                  // :69-79
+      for (size_t i = 0; i < c->n_io; ++i) {
+        Fr w = ldr(io_wires + i * FR);
+        v_s = affine_add(v_s, mul_fr(ldg1(c->vk_io + i * G1W), w));
+        w_s = affine_add(w_s, mul_fr(ldg2(c->wk_io + i * G2W), w));
+        y_s = affine_add(y_s, mul_fr(ldg1(c->yk_io + i * G1W), w));
+      }
+      last[0] = e(v_s, w_s); last[1] = e(ldg1(c->t), ldg2(pf->h_s)); last[2] = e(y_s, one2);
+    } catch (const std::domain_error&) { late = std::current_exception(); }
+    for (int k = 0; k < 4; ++k) if (!(four[2 * k].get() == four[2 * k + 1].get())) return 0;
+    if (late) std::rethrow_exception(late);
+    Fq12 lhs = last[0].get(), rhs = last[1].get() * last[2].get();                           // :81-84
     return lhs == rhs ? 1 : 0;
   } catch (const std::domain_error&) { return -2; }
 }

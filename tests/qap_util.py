@@ -91,6 +91,25 @@ def chain_circuit(n, seed=7):
     return A, B, C, wit, 1
 
 
+def chain_io_circuit(n_io, n=20, seed=7):
+    """chain_circuit(n) with the io / mid split as a parameter: wires [one, w_n, w_{n-1}, .., w_0], of which the first n_io are the io part — the constant
+    one and the last n_io - 1 chain values — and the rest the mid part.  n_io = 0: every wire is mid, the constant one included.  n + 2 wires, so n_io <= n + 2.
+    Returns (A, B, C, witness) with the n x (n + 2) matrices in that wire order."""
+    from zkt_testlib import SplitMix64
+    assert 0 <= n_io <= n + 2
+    rng = SplitMix64(seed)
+    cs = [rng.below(1 << 32) for _ in range(n)]
+    ws = [rng.below(R)]
+    for j in range(n): ws.append((ws[j] * ws[j] + cs[j]) % R)
+    wit = [1] + ws[::-1]
+    cols = n + 2
+    idx = lambda j: 1 + (n - j)                       # wire of w_j
+    A = [[0] * cols for _ in range(n)]; B = [[0] * cols for _ in range(n)]; C = [[0] * cols for _ in range(n)]
+    for j in range(n):
+        A[j][idx(j)] = 1; B[j][idx(j)] = 1; C[j][idx(j + 1)] = 1; C[j][0] = (-cs[j]) % R
+    return A, B, C, wit
+
+
 def bits_circuit(n, seed=7):
     """A witness of 0/1 values (what a real circuit's witness is full of): n-1 booleanity constraints b_j * b_j = b_j and one packing
     constraint (sum_j 2^j b_j) * 1 = out; wires [one, out | b_0 .. b_{n-2}], l = 1.  (A w) and (B w) are 0/1 vectors: the MSM's skew path."""

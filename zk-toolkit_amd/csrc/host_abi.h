@@ -44,6 +44,18 @@ inline int down(void* h, const void* d, size_t bytes, hipStream_t s) { if (bytes
 constexpr size_t G1B = sizeof(zkt_g1_affine), G2B = sizeof(zkt_g2_affine), SPB = sizeof(zkt_secp_affine), FRB = 32;
 inline size_t abi_pt_bytes(int grp) { return grp == G_G1 ? G1B : grp == G_G2 ? G2B : SPB; }
 
+// a 4-limb value that is 0 mod r: 0, r or 2r (3r > 2^256).  Values are reduced on load, so a trapdoor must pass this test, not a test of its raw limbs.
+inline bool fr_is_zero_mod_r(const uint64_t* a) {
+  constexpr uint64_t r[4] = {0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull};
+  uint64_t m[4] = {0, 0, 0, 0};                     // 0, then r, then 2r
+  for (int k = 0; k < 3; ++k) {
+    if (a[0] == m[0] && a[1] == m[1] && a[2] == m[2] && a[3] == m[3]) return true;
+    unsigned __int128 c = 0;
+    for (int j = 0; j < 4; ++j) { c += (unsigned __int128)m[j] + r[j]; m[j] = (uint64_t)c; c >>= 64; }
+  }
+  return false;
+}
+
 // The standard generators in the ABI layout (canonical coordinates, little-endian u64 limbs)
 constexpr zkt_g1_affine G1_GEN = {                                            // g1_point.rs:38-47
     {0xfb3af00adb22c6bbull, 0x6c55e83ff97a1aefull, 0xa14e3a3f171bac58ull, 0xc3688c4f9774b905ull, 0x2695638c4fa9ac0full, 0x17f1d3a73197d794ull},

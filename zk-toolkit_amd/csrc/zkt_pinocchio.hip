@@ -197,7 +197,7 @@ extern "C" {
 int zkt_pinocchio_setup(zkt_pinocchio_crs* c, const uint64_t* vi, const uint64_t* wi, const uint64_t* yi, const uint64_t* rnd) {
   if (zkt_internal_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
   if (!c || !vi || !wi || !yi || !rnd || c->n == 0 || c->max_degree == 0) return ZKT_ERR_SHAPE;
-  for (int k = 0; k < 8; ++k) { bool z = true; for (int j = 0; j < 4; ++j) z = z && rnd[4 * k + j] == 0; if (z) return ZKT_ERR_INV_ZERO; }   // rand_elem(true) (crs.rs:58-64,82)
+  for (int k = 0; k < 8; ++k) if (fr_is_zero_mod_r(rnd + 4 * k)) return ZKT_ERR_INV_ZERO;   // rand_elem(true) (crs.rs:58-64,82); the kernels reduce on load, so r and 2r are zero too
   const size_t n = c->n, nio = c->n_io, nmid = c->n_mid, rows = nio + nmid, deg = c->max_degree;
   if (rows == 0) return ZKT_ERR_SHAPE;
   hipStream_t s = nullptr;

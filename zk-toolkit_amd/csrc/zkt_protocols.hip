@@ -484,7 +484,7 @@ int zkt_groth16_setup(zkt_groth16_crs* c, const uint64_t* ui, const uint64_t* vi
   const size_t n = c->n, l = c->l, m = c->m, rows = m + 1;
   hipStream_t s = nullptr;
   uint64_t trap[20]; memcpy(trap, alpha, 32); memcpy(trap + 4, beta, 32); memcpy(trap + 8, gamma, 32); memcpy(trap + 12, delta, 32); memcpy(trap + 16, x, 32);
-  for (int k = 0; k < 5; ++k) { bool z = true; for (int j = 0; j < 4; ++j) z = z && trap[4 * k + j] == 0; if (z) return ZKT_ERR_INV_ZERO; }   // rand_elem(true): non-zero (crs.rs:59-63)
+  for (int k = 0; k < 5; ++k) if (fr_is_zero_mod_r(trap + 4 * k)) return ZKT_ERR_INV_ZERO;   // rand_elem(true): non-zero (crs.rs:59-63); the kernels reduce on load, so r and 2r are zero too
   Dev dP(rows * n * FRB), dtrap(160), due(rows * FRB), dve(rows * FRB), dwe(rows * FRB), dy(rows * FRB), dxp(n * FRB), dxt(n * FRB);
   Dev dgen1(G1B), dgen2(G2B), dout1((rows + 2 * n + 3) * G1B), dout2((n + 3) * G2B), dgt(576), derr(8);
   int rc;
