@@ -81,6 +81,30 @@ impl CRS {
                                               t.delta.limbs.as_ptr(), t.x.limbs.as_ptr()) });
         buf.into_crs(n, l, m)
     }
+    /// CRS::new (crs.rs:49-146) from a device-resident QAP (qap::QAP::build): n and m are the handle's, ui / vi / wi are read where they were built
+    pub fn new_from_qap(l: usize, qap: &crate::qap::QAP, t: &Trapdoor) -> Self {
+        init();
+        let (n, m) = (qap.num_constraints, qap.num_witness_values - 1);
+        let mut buf = CrsBuf::new(n, l, m);
+        let mut view = buf.view(n, l, m);
+        check(unsafe { ffi::zkt_groth16_setup_resident(&mut view, qap.raw(), t.alpha.limbs.as_ptr(), t.beta.limbs.as_ptr(), t.gamma.limbs.as_ptr(), t.delta.limbs.as_ptr(),
+                                                       t.x.limbs.as_ptr()) });
+        buf.into_crs(n, l, m)
+    }
+}
+
+/// Prover::new + Prover::prove (prover.rs:50-147) from a device-resident QAP: the quotient is computed on the device; panics with the reference's
+/// "p should be divisible by t" when the wires do not satisfy the constraints
+pub fn prove_from_qap(crs: &CRS, qap: &crate::qap::QAP, wires: &[Fr], r: &Fr, s: &Fr) -> Proof {
+    init();
+    let mut buf = CrsBuf::from_crs(crs);
+    let view = buf.view(crs.n, crs.l, crs.m);
+    let w = Fr::flatten(wires);
+    let (mut a, mut b, mut c) = (G1Point::zero_raw(), G2Point::zero_raw(), G1Point::zero_raw());
+    let rc = unsafe { ffi::zkt_groth16_prove_resident(&view, qap.raw(), w.as_ptr(), r.limbs.as_ptr(), s.limbs.as_ptr(), &mut a, &mut b, &mut c) };
+    if rc == ffi::ZKT_ERR_REMAINDER { panic!("p should be divisible by t"); }
+    check(rc);
+    Proof { A: G1Point::from_raw(&a), B: G2Point::from_raw(&b), C: G1Point::from_raw(&c) }
 }
 
 /// prover.rs:35-46.  Polynomials are coefficient vectors, low degree first; `Prover::new` (equation parser -> gates -> R1CS -> QAP, prover.rs:48-94) is the

@@ -6,6 +6,7 @@
 //!   `G1Point`, `G2Point`   building_block/curves/bls12_381/{g1_point,g2_point}.rs, curves/macros.rs
 //!   `GTPoint`, `Pairing`   building_block/curves/bls12_381/{gt_point,pairing}.rs
 //!   `Polynomial`           building_block/field/polynomial.rs:271-293 (eval_with_g1_hidings / eval_with_g2_hidings)
+//!   `QAP`                  zk/w_trusted_setup/qap/qap.rs:137-217 (build, is_valid), resident on the device
 //!   `groth16::*`           zk/w_trusted_setup/groth16/zktoolkit_based/{crs,prover,verifier,proof}.rs
 //!   `Bulletproofs`         zk/wo_trusted_setup/bulletproofs.rs
 //!   `pinocchio::*`         zk/w_trusted_setup/pinocchio/{crs,prover,verifier,proof,witness}.rs
@@ -23,6 +24,7 @@ pub mod tower;
 pub mod points;
 pub mod pairing;
 pub mod polynomial;
+pub mod qap;
 pub mod groth16;
 pub mod bulletproofs;
 pub mod signature;
@@ -35,6 +37,7 @@ pub use tower::{Fq2, Fq6, Fq12};
 pub use points::{AffinePoint, AffinePoints, G1Point, G2Point, SecpPoint};
 pub use pairing::{GTPoint, Pairing};
 pub use polynomial::{Polynomial, G1Bases, G2Bases};
+pub use qap::QAP;
 pub use bulletproofs::Bulletproofs;
 pub use signature::{PrivateKey, Signer};
 /// the reference crate's own module paths (`building_block::curves::bls12_381::g1_point::G1Point`, `zk::w_trusted_setup::groth16::zktoolkit_based::prover::Prover`, ...)

@@ -491,6 +491,34 @@ int zkt_groth16_setup_r1cs_sharded(size_t n, size_t l, size_t m, const zkt_spars
 int zkt_groth16_prove_r1cs_partials(zkt_groth16_pk* pk, const uint64_t* dev_wires, const uint64_t* r, const uint64_t* s, uint32_t* dev_partials);
 void zkt_groth16_pk_free(zkt_groth16_pk* pk);
 
+/* ---- R1CS -> QAP on the device, and the dense (coefficient-form) Groth16 path from a resident QAP -----------------------------------------
+ * QAP::build qap/qap.rs:137-203 (build_polynomial :33-97): the Lagrange interpolation of every wire's column of A, B and C over the domain {1..n}.  A, B, C are the
+ * R1CS in the CSR form of zkt_groth16_setup_r1cs (zkt_sparse_rows above: n rows, column indices below cols = m + 1; values reduced on load; entries with the same
+ * (row, col) add).  ui, vi, wi get cols x n coefficients each, low degree first, canonical, zero-padded as the dense entry points take them; a wire in no
+ * constraint gets n zeros.  The interpolant is unique, so the coefficients are the reference's bit for bit.
+ * ZKT_ERR_SHAPE, before anything is allocated or launched and with the outputs untouched: a null pointer, n == 0, cols == 0, n > ZKT_QAP_MAX_N,
+ * cols * n > ZKT_QAP_MAX_CELLS, rowptr[0] != 0, a decreasing rowptr, 2^32 - 1 or more entries, or col[k] >= cols; zkt_last_error_index() is the constraint row of
+ * the first offending entry where there is one (A, then B, then C). */
+#define ZKT_QAP_MAX_N     ((size_t)8192)      /* constraints: the build keeps an n x n table of basis coefficients */
+#define ZKT_QAP_MAX_CELLS ((size_t)1 << 26)   /* cols * n: coefficients of one of the three arrays (2 GiB) */
+typedef struct zkt_qap zkt_qap;
+/* QAP::build: blocking, host pointers */
+int zkt_qap_build(size_t n, size_t cols, const zkt_sparse_rows* A, const zkt_sparse_rows* B, const zkt_sparse_rows* C,
+                  uint64_t* ui, uint64_t* vi, uint64_t* wi);
+/* the same, kept on the device: the handle holds ui, vi, wi and serves the _resident calls below, any number of times, until zkt_qap_free */
+int zkt_qap_create(size_t n, size_t cols, const zkt_sparse_rows* A, const zkt_sparse_rows* B, const zkt_sparse_rows* C, zkt_qap** out);
+/* the handle's arrays back to the host (what zkt_pinocchio_setup takes as vi, wi, yi); any of the three may be NULL */
+int zkt_qap_download(const zkt_qap* q, uint64_t* ui, uint64_t* vi, uint64_t* wi);
+void zkt_qap_free(zkt_qap* q);   /* NULL is a no-op */
+/* QAP::is_valid / build_p qap.rs:99-112, CRS::new crs.rs:49-146 and Prover::new + prove prover.rs:50-147 with ui, vi, wi read from the handle in place:
+ * zkt_qap_quotient (rows = cols), zkt_groth16_setup and zkt_groth16_prove_qap, with the same results, statuses and zkt_last_error_index() values.
+ * The CRS calls need q's n == crs->n and q's cols == crs->m + 1: otherwise ZKT_ERR_SHAPE, outputs untouched. */
+int zkt_qap_quotient_resident(const zkt_qap* q, const uint64_t* wires /* cols */, uint64_t* h /* n-1 */);
+int zkt_groth16_setup_resident(zkt_groth16_crs* crs, const zkt_qap* q, const uint64_t* alpha, const uint64_t* beta,
+                               const uint64_t* gamma, const uint64_t* delta, const uint64_t* x);
+int zkt_groth16_prove_resident(const zkt_groth16_crs* crs, const zkt_qap* q, const uint64_t* wires,
+                               const uint64_t* r, const uint64_t* s, zkt_g1_affine* A, zkt_g2_affine* B, zkt_g1_affine* C);
+
 /* ---- multi-GPU: one process per GPU -------------------------------------------------------------------------------
  * The index range of an MSM (or of the three resident base sets of a Groth16 key) is partitioned over the ranks; every rank computes the
  * Jacobian partial sum of its shard; the only exchange is ONE all-gather of the fixed-size partials (168 B G1, 336 B G2, 672 B per proof)
@@ -539,6 +567,9 @@ int zkt_fq_mul_batch_dev(const uint64_t* dev_a, const uint64_t* dev_b, uint64_t*
  * of the last zkt_g1_msm_dev / zkt_tate_batch_dev call on this thread, and its name */
 float zkt_last_kernel_ms(void);
 const char* zkt_last_kernel_name(void);
+/* device time (ms, HIP events around the two launches) of k_qap_basis and k_qap_columns in the last zkt_qap_create / zkt_qap_build on this thread;
+ * either pointer may be NULL (tools/diag/qap_build_timing.py) */
+void zkt_qap_last_build_ms(float* basis_ms, float* columns_ms);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,7 @@ def lib():
         # size_t arguments beyond the sixth travel on the stack: declare them, or ctypes pushes a 32-bit int with garbage above it
         vp = ctypes.c_void_p
         L.zkt_groth16_verify_batch.argtypes = [vp, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp]
+        L.zkt_groth16_setup.argtypes = [vp] * 9
         L.zkt_groth16_prove.argtypes = [vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp, vp, vp]
         L.zkt_groth16_setup_r1cs.argtypes = [ctypes.c_size_t] * 3 + [vp] * 10
         L.zkt_groth16_prove_r1cs.argtypes = [vp] * 7
@@ -99,6 +100,14 @@ def lib():
         L.zkt_qap_build_t.argtypes = [sz, vp]
         L.zkt_qap_quotient.argtypes = [vp, vp, vp, sz, sz, vp, vp]
         L.zkt_groth16_prove_qap.argtypes = [vp] * 10
+        L.zkt_qap_build.argtypes = [sz, sz] + [vp] * 6
+        L.zkt_qap_create.argtypes = [sz, sz] + [vp] * 4
+        L.zkt_qap_download.argtypes = [vp] * 4
+        L.zkt_qap_free.argtypes = [vp]; L.zkt_qap_free.restype = None
+        L.zkt_qap_quotient_resident.argtypes = [vp] * 3
+        L.zkt_groth16_setup_resident.argtypes = [vp] * 7
+        L.zkt_groth16_prove_resident.argtypes = [vp] * 8
+        L.zkt_qap_last_build_ms.argtypes = [vp, vp]; L.zkt_qap_last_build_ms.restype = None
         _lib = L
     return _lib
 

@@ -27,6 +27,8 @@
 #include "zkt_internal.h"
 #include "../../include/zkt.h"
 #include "host_abi.h"
+#include "fr_pool.h"
+#include "qap_handle.h"
 
 namespace zkt {
 namespace {
@@ -218,20 +220,6 @@ __global__ void __launch_bounds__(256) k_wire_comb(Comb3 c, const uint32_t* __re
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// stream-ordered scratch of one call: taken on the call's stream, given back on it when the call's frame ends
-struct Pool {
-  hipStream_t s; std::vector<void*> ptrs;
-  explicit Pool(hipStream_t s_) : s(s_) {}
-  uint32_t* get(size_t elems) {
-    void* p = nullptr;
-    if (hipMallocAsync(&p, (elems ? elems : 1) * FRB, s) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    ptrs.push_back(p); return (uint32_t*)p;
-  }
-  ~Pool() { for (void* p : ptrs) (void)hipFreeAsync(p, s); }
-  Pool(const Pool&) = delete; Pool& operator=(const Pool&) = delete;
-};
-#define PGET(var, pool, elems) uint32_t* var = (pool).get(elems); if (!var) return ZKT_ERR_DEVICE
-
 // twiddle tables per transform size, kept until zkt_shutdown
 struct Tw { uint32_t *tw = nullptr, *twinv = nullptr, *ninv = nullptr; };
 std::mutex g_tw_mu;
@@ -355,7 +343,8 @@ int divrem_dev(Pool& pool, const uint32_t* a, size_t na, const uint32_t* b, size
   HIPCHK(hipGetLastError()); return ZKT_OK;
 }
 
-// out[0 .. n] = the coefficients of prod_{i=1..n} (x - i), Montgomery
+}  // namespace
+// out[0 .. n] = the coefficients of prod_{i=1..n} (x - i), Montgomery (fr_pool.h: zkt_qap.hip divides it by every x - j)
 int build_t_dev(Pool& pool, size_t n, uint32_t* out) {
   hipStream_t s = pool.s;
   if (n == 0) {                                            // the empty product
@@ -385,6 +374,7 @@ int build_t_dev(Pool& pool, size_t n, uint32_t* out) {
   HIPCHK(hipGetLastError()); return ZKT_OK;
 }
 
+namespace {
 bool lead_is_zero(const uint64_t* w) {                     // 0, r or 2r: the 256-bit integers that are zero mod r
   static const uint64_t R1[4] = {0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull};
   static const uint64_t R2[4] = {0xfffffffe00000002ull, 0xa77b4805fffcb7fdull, 0x6673b0101343b00aull, 0xe7db4ea6533afa90ull};
@@ -408,16 +398,13 @@ int quotient_dev(Pool& pool, const uint32_t* U, const uint32_t* V, const uint32_
   HIPCHK(hipGetLastError()); return ZKT_OK;
 }
 
-// uploads ui, vi, wi, wires and leaves U, V, W (Montgomery) and h; returns ZKT_ERR_REMAINDER (+ index) when t does not divide p
-int qap_quotient_host(Pool& pool, const uint64_t* ui, const uint64_t* vi, const uint64_t* wi, size_t rows, size_t n, const uint64_t* wires,
-                      uint32_t** U, uint32_t** V, uint32_t** h) {
+// ui, vi, wi on the device in the caller's layout (rows x n); uploads the wires and leaves U, V, W (Montgomery) and h; returns ZKT_ERR_REMAINDER (+ index) when t does not divide p
+int qap_quotient_dev(Pool& pool, const uint32_t* du, const uint32_t* dv, const uint32_t* dwi, size_t rows, size_t n, const uint64_t* wires,
+                     uint32_t** U, uint32_t** V, uint32_t** h) {
   hipStream_t s = pool.s;
-  PGET(dw, pool, rows); PGET(du, pool, rows * n); PGET(dv, pool, rows * n); PGET(dwi, pool, rows * n);
+  PGET(dw, pool, rows);
   PGET(cu, pool, n); PGET(cv, pool, n); PGET(cw, pool, n); PGET(dh, pool, n); PGET(flags, pool, 1);
   HIPCHK(hipMemcpyAsync(dw, wires, rows * FRB, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(du, ui, rows * n * FRB, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(dv, vi, rows * n * FRB, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(dwi, wi, rows * n * FRB, hipMemcpyHostToDevice, s));
   unsigned long long init[2] = {0, NO_ERR}, got[2];         // [0]: 1 + degree of the remainder; [1]: a zero leading coefficient (t is monic: never)
   HIPCHK(hipMemcpyAsync(flags, init, 16, hipMemcpyHostToDevice, s));
   Comb3 c; c.m[0] = du; c.m[1] = dv; c.m[2] = dwi; c.out[0] = cu; c.out[1] = cv; c.out[2] = cw;
@@ -429,13 +416,25 @@ int qap_quotient_host(Pool& pool, const uint64_t* ui, const uint64_t* vi, const 
   *U = cu; *V = cv; *h = dh;
   return ZKT_OK;
 }
-int store_host(uint64_t* dst, const uint32_t* src, size_t cnt, Pool& pool) {         // Montgomery device values -> canonical host words (queued)
+// the same from host arrays: their uploads, then qap_quotient_dev
+int qap_quotient_host(Pool& pool, const uint64_t* ui, const uint64_t* vi, const uint64_t* wi, size_t rows, size_t n, const uint64_t* wires,
+                      uint32_t** U, uint32_t** V, uint32_t** h) {
+  hipStream_t s = pool.s;
+  PGET(du, pool, rows * n); PGET(dv, pool, rows * n); PGET(dwi, pool, rows * n);
+  HIPCHK(hipMemcpyAsync(du, ui, rows * n * FRB, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dv, vi, rows * n * FRB, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dwi, wi, rows * n * FRB, hipMemcpyHostToDevice, s));
+  return qap_quotient_dev(pool, du, dv, dwi, rows, n, wires, U, V, h);
+}
+}  // namespace
+int store_host(uint64_t* dst, const uint32_t* src, size_t cnt, Pool& pool) {         // Montgomery device values -> canonical host words (queued; fr_pool.h)
   if (!cnt) return ZKT_OK;
   PGET(tmp, pool, cnt);
   gather<false, true>(tmp, cnt, src, cnt, 0, 1, nullptr, 0, pool.s);
   HIPCHK(hipMemcpyAsync(dst, tmp, cnt * FRB, hipMemcpyDeviceToHost, pool.s));
   return ZKT_OK;
 }
+namespace {
 bool mul_shape_ok(const void* a, size_t na, const void* b, size_t nb, const void* out) {
   return a && b && out && na && nb && na <= ZKT_POLY_MAX_LEN && nb <= ZKT_POLY_MAX_LEN && na + nb - 1 <= ZKT_POLY_MAX_LEN;
 }
@@ -544,17 +543,35 @@ int zkt_qap_quotient(const uint64_t* ui, const uint64_t* vi, const uint64_t* wi,
   return ZKT_OK;
 }
 
-// Prover::new + Prover::prove (prover.rs:50-147): the quotient on the device, then the sums and single multiplications exactly as zkt_groth16_prove forms them
-int zkt_groth16_prove_qap(const zkt_groth16_crs* c, const uint64_t* ui, const uint64_t* vi, const uint64_t* wi, const uint64_t* wires,
-                          const uint64_t* r, const uint64_t* s_, zkt_g1_affine* A, zkt_g2_affine* B, zkt_g1_affine* C) {
-  if (!c || !ui || !vi || !wi || !wires || !r || !s_ || !A || !B || !C || c->n == 0 || c->l > c->m || 2 * c->n - 1 > ZKT_POLY_MAX_LEN || c->m + 1 > ZKT_POLY_MAX_LEN) return ZKT_ERR_SHAPE;
+// QAP::is_valid / Prover::new on a resident QAP (qap.rs:99-112, prover.rs:64-71): zkt_qap_quotient with the three arrays read from the handle
+int zkt_qap_quotient_resident(const zkt_qap* q, const uint64_t* wires, uint64_t* h) {
+  if (!q || !wires || (q->n > 1 && !h) || 2 * q->n - 1 > ZKT_POLY_MAX_LEN || q->cols > ZKT_POLY_MAX_LEN) return ZKT_ERR_SHAPE;
   if (zkt_internal_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  Pool pool(nullptr);
+  uint32_t *U, *V, *dh;
+  ZCHK(qap_quotient_dev(pool, q->m[0], q->m[1], q->m[2], q->cols, q->n, wires, &U, &V, &dh));
+  ZCHK(store_host(h, dh, q->n - 1, pool));
+  HIPCHK(hipStreamSynchronize(pool.s));
+  return ZKT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+bool prove_qap_shape_ok(const zkt_groth16_crs* c, const void* wires, const void* r, const void* s_, const void* A, const void* B, const void* C) {
+  return c && wires && r && s_ && A && B && C && c->n != 0 && c->l <= c->m && 2 * c->n - 1 <= ZKT_POLY_MAX_LEN && c->m + 1 <= ZKT_POLY_MAX_LEN;
+}
+// Prover::new + Prover::prove (prover.rs:50-147): the quotient on the device (from host arrays, or from device arrays when du is given), then the sums and single
+// multiplications exactly as zkt_groth16_prove forms them
+int prove_qap(const zkt_groth16_crs* c, const uint64_t* ui, const uint64_t* vi, const uint64_t* wi, const uint32_t* du, const uint32_t* dv, const uint32_t* dwi,
+              const uint64_t* wires, const uint64_t* r, const uint64_t* s_, zkt_g1_affine* A, zkt_g2_affine* B, zkt_g1_affine* C) {
   const size_t n = c->n, l = c->l, m = c->m, rows = m + 1, nw = m - l;
   std::vector<uint64_t> U(n * 4), V(n * 4), H((n > 1 ? n - 1 : 1) * 4);
   {
     Pool pool(nullptr);
     uint32_t *dU, *dV, *dh;
-    ZCHK(qap_quotient_host(pool, ui, vi, wi, rows, n, wires, &dU, &dV, &dh));
+    if (du) ZCHK(qap_quotient_dev(pool, du, dv, dwi, rows, n, wires, &dU, &dV, &dh));
+    else ZCHK(qap_quotient_host(pool, ui, vi, wi, rows, n, wires, &dU, &dV, &dh));
     ZCHK(store_host(U.data(), dU, n, pool)); ZCHK(store_host(V.data(), dV, n, pool)); ZCHK(store_host(H.data(), dh, n - 1, pool));
     HIPCHK(hipStreamSynchronize(pool.s));
   }
@@ -574,6 +591,23 @@ int zkt_groth16_prove_qap(const zkt_groth16_crs* c, const uint64_t* ui, const ui
       (rc = zkt_g1_add_batch(&t1, &ndrs, &oC, 1))) return rc;                                                                          // C
   *A = oA; *B = oB; *C = oC;
   return ZKT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int zkt_groth16_prove_qap(const zkt_groth16_crs* c, const uint64_t* ui, const uint64_t* vi, const uint64_t* wi, const uint64_t* wires,
+                          const uint64_t* r, const uint64_t* s_, zkt_g1_affine* A, zkt_g2_affine* B, zkt_g1_affine* C) {
+  if (!ui || !vi || !wi || !prove_qap_shape_ok(c, wires, r, s_, A, B, C)) return ZKT_ERR_SHAPE;
+  if (zkt_internal_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  return prove_qap(c, ui, vi, wi, nullptr, nullptr, nullptr, wires, r, s_, A, B, C);
+}
+// the same with ui, vi, wi read from a resident QAP
+int zkt_groth16_prove_resident(const zkt_groth16_crs* c, const zkt_qap* q, const uint64_t* wires, const uint64_t* r, const uint64_t* s_,
+                               zkt_g1_affine* A, zkt_g2_affine* B, zkt_g1_affine* C) {
+  if (!q || !prove_qap_shape_ok(c, wires, r, s_, A, B, C) || q->n != c->n || q->cols != c->m + 1) return ZKT_ERR_SHAPE;
+  if (zkt_internal_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  return prove_qap(c, nullptr, nullptr, nullptr, q->m[0], q->m[1], q->m[2], wires, r, s_, A, B, C);
 }
 
 }  // extern "C"

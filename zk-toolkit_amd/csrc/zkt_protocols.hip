@@ -13,6 +13,7 @@
 #include "zkt_internal.h"
 #include "../../include/zkt.h"
 #include "host_abi.h"
+#include "qap_handle.h"
 
 namespace zkt {
 
@@ -476,23 +477,24 @@ std::shared_ptr<void> ate_key_now(const zkt_groth16_crs* c, size_t n_stmt, const
 }  // namespace
 extern "C" {
 
-// CRS::new (crs.rs:49-146), trapdoors injected.  ui/vi/wi: (m+1) x n Fr coefficients, low degree first.
-int zkt_groth16_setup(zkt_groth16_crs* c, const uint64_t* ui, const uint64_t* vi, const uint64_t* wi,
-                      const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, const uint64_t* delta, const uint64_t* x) {
-  if (zkt_internal_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!c || !ui || !vi || !wi || !alpha || !beta || !gamma || !delta || !x || c->n == 0 || c->l > c->m) return ZKT_ERR_SHAPE;
+}  // extern "C"
+namespace {
+// CRS::new (crs.rs:49-146), trapdoors injected.  hp: ui/vi/wi on the host, uploaded one after the other into one buffer; or dp: the same three arrays already on
+// the device (a resident QAP), read in place.  (m+1) x n Fr coefficients each, low degree first.
+int groth16_setup(zkt_groth16_crs* c, const uint64_t* const hp[3], const uint32_t* const dp[3],
+                  const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, const uint64_t* delta, const uint64_t* x) {
   const size_t n = c->n, l = c->l, m = c->m, rows = m + 1;
   hipStream_t s = nullptr;
   uint64_t trap[20]; memcpy(trap, alpha, 32); memcpy(trap + 4, beta, 32); memcpy(trap + 8, gamma, 32); memcpy(trap + 12, delta, 32); memcpy(trap + 16, x, 32);
   for (int k = 0; k < 5; ++k) if (fr_is_zero_mod_r(trap + 4 * k)) return ZKT_ERR_INV_ZERO;   // rand_elem(true): non-zero (crs.rs:59-63); the kernels reduce on load, so r and 2r are zero too
-  Dev dP(rows * n * FRB), dtrap(160), due(rows * FRB), dve(rows * FRB), dwe(rows * FRB), dy(rows * FRB), dxp(n * FRB), dxt(n * FRB);
+  Dev dP(hp ? rows * n * FRB : 0), dtrap(160), due(rows * FRB), dve(rows * FRB), dwe(rows * FRB), dy(rows * FRB), dxp(n * FRB), dxt(n * FRB);
   Dev dgen1(G1B), dgen2(G2B), dout1((rows + 2 * n + 3) * G1B), dout2((n + 3) * G2B), dgt(576), derr(8);
   int rc;
   if ((rc = up(dtrap, trap, 160, s)) || (rc = up(dgen1, &G1_GEN, G1B, s)) || (rc = up(dgen2, &G2_GEN, G2B, s))) return rc;
-  const uint64_t* polys[3] = {ui, vi, wi}; Dev* evals[3] = {&due, &dve, &dwe};
+  Dev* evals[3] = {&due, &dve, &dwe};
   for (int k = 0; k < 3; ++k) {
-    if ((rc = up(dP, polys[k], rows * n * FRB, s))) return rc;
-    fr_eval_rows(dP.w(), rows, n, dtrap.w() + 32, evals[k]->w(), s);
+    if (hp && (rc = up(dP, hp[k], rows * n * FRB, s))) return rc;
+    fr_eval_rows(hp ? dP.w() : dp[k], rows, n, dtrap.w() + 32, evals[k]->w(), s);
   }
   hipLaunchKernelGGL(k_groth16_setup_scalars, dim3(1), dim3(64), 0, s, (const uint32_t*)due.w(), (const uint32_t*)dve.w(), (const uint32_t*)dwe.w(),
                      (const uint32_t*)dtrap.w(), n, l, m, dy.w(), dxp.w(), dxt.w());
@@ -519,6 +521,23 @@ int zkt_groth16_setup(zkt_groth16_crs* c, const uint64_t* ui, const uint64_t* vi
       (rc = down(c->g2_delta, o2 + (n + 2) * 50, G2B, s)) || (rc = down(c->gt_alpha_beta, dgt.p, 576, s))) return rc;
   HIPCHK(hipStreamSynchronize(s));
   return ZKT_OK;
+}
+}  // namespace
+extern "C" {
+
+int zkt_groth16_setup(zkt_groth16_crs* c, const uint64_t* ui, const uint64_t* vi, const uint64_t* wi,
+                      const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, const uint64_t* delta, const uint64_t* x) {
+  if (zkt_internal_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!c || !ui || !vi || !wi || !alpha || !beta || !gamma || !delta || !x || c->n == 0 || c->l > c->m) return ZKT_ERR_SHAPE;
+  const uint64_t* hp[3] = {ui, vi, wi};
+  return groth16_setup(c, hp, nullptr, alpha, beta, gamma, delta, x);
+}
+// the same with ui, vi, wi read from a resident QAP (zkt_qap_create): nothing of size (m+1) x n is uploaded
+int zkt_groth16_setup_resident(zkt_groth16_crs* c, const zkt_qap* q, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, const uint64_t* delta,
+                               const uint64_t* x) {
+  if (!c || !q || !alpha || !beta || !gamma || !delta || !x || c->n == 0 || c->l > c->m || q->n != c->n || q->cols != c->m + 1) return ZKT_ERR_SHAPE;
+  if (zkt_internal_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  return groth16_setup(c, nullptr, q->m, alpha, beta, gamma, delta, x);
 }
 
 // Prover::prove (prover.rs:96-147), r and s injected.
