@@ -161,7 +161,11 @@ pub mod building_block {
         pub mod secp256k1 {
             pub mod affine_point { pub use crate::points::AffinePoint; }
             pub mod affine_points { pub use crate::points::AffinePoints; }
+            pub mod ecdsa { pub use crate::ecdsa::{Ecdsa, Signature}; }
         }
+    }
+    pub mod hasher {
+        pub mod sha256 { pub use crate::ecdsa::Sha256; }
     }
 }
 pub mod zk {

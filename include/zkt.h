@@ -303,6 +303,38 @@ int zkt_bls_public_keys_batch(const uint64_t* sks, size_t n, zkt_g1_affine* pks)
 int zkt_bls_sign_batch(const uint8_t* msgs, const uint64_t* offsets, const uint64_t* sks, size_t n, zkt_g2_affine* sigs);
 int zkt_bls_verify_batch(const uint8_t* msgs, const uint64_t* offsets, const zkt_g2_affine* sigs, const zkt_g1_affine* pks, size_t n, uint32_t* ok);
 
+/* SHA-256 and secp256k1 ECDSA (hasher/sha256.rs, curves/secp256k1/ecdsa.rs): one message / one signature per lane, one launch per call.
+ * Messages are n byte strings, concatenated, offsets[n+1], as the BLS calls take them; an element whose end lies before its start is an empty message.
+ * msgs may be NULL only if no offset is above 0 (ZKT_ERR_SHAPE otherwise).
+ * Signature ecdsa.rs:16-20.  r and s are 256-bit integers in 4 little-endian limbs.  NOT "reduced on load": unlike every other 4-limb value of this
+ * header, verification takes r and s as given and compares them with n, as ecdsa.rs:105-112 does (r + n is a different signature, and an invalid one);
+ * signing writes canonical r, s in [1, n-1]. */
+typedef struct { uint64_t r[4], s[4]; } zkt_ecdsa_sig;   /* 64 B */
+/* Hasher::get_digest of Sha256 (sha256.rs:75-81; pad_msg / compute_hash sha_common.rs:157-186): digests = n x 32 bytes, the eight state words big-endian as
+ * to_u8_array writes them (sha256.rs:10-22).  A message runs serially on its lane: the batch is the parallelism, a single long message gets one lane. */
+int zkt_sha256_batch(const uint8_t* msgs, const uint64_t* offsets, size_t n, uint8_t* digests);
+/* Ecdsa::gen_pub_key ecdsa.rs:33-35: pks[i] = generator * sks[i] through the generator's comb table (sks: 4 limbs each, any 256-bit value) */
+int zkt_ecdsa_public_keys_batch(const uint64_t* sks, size_t n, zkt_secp_affine* pks);
+/* Ecdsa::sign ecdsa.rs:37-85 with the nonce injected (the reference draws k at :51): z = the digest as a big-endian integer mod n (:55, :73), r = x(k G) mod n (:64),
+ * s = k^-1 (z + r d) (:71-74).  sks, ks: 4-limb sn elements, reduced mod n on load as PrimeFieldElem::new does.  retry[i] = 1 where the reference's loop would draw
+ * another k — k = 0 mod n (k G at infinity, :61), r == 0 (:67), s == 0 (:77) — and sigs[i] is then all zero; the call still returns ZKT_OK.  retry may be NULL
+ * only if no element needs one: otherwise ZKT_ERR_SHAPE with zkt_last_error_index() = the first such element.  The message form hashes on the device (the
+ * digest form behind zkt_sha256_batch's kernel, no host round trip). */
+int zkt_ecdsa_sign_digest_batch(const uint8_t* digests, const uint64_t* sks, const uint64_t* ks, size_t n, zkt_ecdsa_sig* sigs, uint32_t* retry);
+int zkt_ecdsa_sign_batch(const uint8_t* msgs, const uint64_t* offsets, const uint64_t* sks, const uint64_t* ks, size_t n, zkt_ecdsa_sig* sigs, uint32_t* retry);
+/* Ecdsa::verify ecdsa.rs:88-135: ok[i] = 1/0, never a per-element error.  ok = 0 for a public key at infinity (:94) or off the curve (:98; coordinates are loaded
+ * exactly as zkt_secp_is_on_curve_batch loads them), for r or s equal to 0 or not below n (:105-112, r and s taken as given), for u1 G + u2 Q at infinity (:129) and
+ * for r != x mod n (:131).  A digest that is not below n is legal: z is reduced mod n (:117).  The test n * pub_key == infinity (:102) is not evaluated: the curve has
+ * cofactor 1, so it holds for every point of the curve.  u1 G + u2 Q is one projective accumulator (generator comb table + a per-lane window table of Q); the final
+ * comparison is X == r Z^2 or, when r + n < p, X == (r + n) Z^2, so no inversion follows the one of s.  Null pointers: ZKT_ERR_SHAPE; n == 0: ZKT_OK. */
+int zkt_ecdsa_verify_digest_batch(const uint8_t* digests, const zkt_ecdsa_sig* sigs, const zkt_secp_affine* pks, size_t n, uint32_t* ok);
+int zkt_ecdsa_verify_batch(const uint8_t* msgs, const uint64_t* offsets, const zkt_ecdsa_sig* sigs, const zkt_secp_affine* pks, size_t n, uint32_t* ok);
+/* the digest form on device pointers, asynchronous and ordered on `stream` (dev_ok is complete when the stream reaches that point).
+ * ONE exception: the first ECDSA call of a process (any of them; again after zkt_shutdown) builds the generator's comb table — for this call on `stream`, with a small
+ * upload and a wait for that stream — so that call blocks for ~5 ms and must not be made while `stream` is being captured into a graph.  A host that captures
+ * makes one blocking call first (zkt_ecdsa_public_keys_batch with n = 1 builds the table); every later call only launches. */
+int zkt_ecdsa_verify_digest_batch_dev(const uint8_t* dev_digests, const zkt_ecdsa_sig* dev_sigs, const zkt_secp_affine* dev_pks, size_t n, uint32_t* dev_ok, void* stream);
+
 /* f-4: Pinocchio (protocol 2 of eprint 2013/279) — CRS (EvaluationKeys crs.rs:12-22, VerificationKeys crs.rs:24-39), CRS::new crs.rs:49-161,
  * Prover::prove pinocchio/prover.rs:98-170, Verifier::verify pinocchio/verifier.rs:31-85, Proof proof.rs:6-17.  vi/wi/yi are the
  * (n_io + n_mid) x n dense Fr coefficient arrays of Prover.vi/wi/yi (prover.rs:43-45), low degree first; wires 0..n_io-1 are

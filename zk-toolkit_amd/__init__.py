@@ -108,6 +108,14 @@ def lib():
         L.zkt_groth16_setup_resident.argtypes = [vp] * 7
         L.zkt_groth16_prove_resident.argtypes = [vp] * 8
         L.zkt_qap_last_build_ms.argtypes = [vp, vp]; L.zkt_qap_last_build_ms.restype = None
+        # SHA-256 and ECDSA: every pointer and size declared (an undeclared pointer travels as a 32-bit int: profiles/qap_build_timing.md)
+        L.zkt_sha256_batch.argtypes = [vp, vp, sz, vp]
+        L.zkt_ecdsa_public_keys_batch.argtypes = [vp, sz, vp]
+        L.zkt_ecdsa_sign_digest_batch.argtypes = [vp, vp, vp, sz, vp, vp]
+        L.zkt_ecdsa_sign_batch.argtypes = [vp, vp, vp, vp, sz, vp, vp]
+        L.zkt_ecdsa_verify_digest_batch.argtypes = [vp, vp, vp, sz, vp]
+        L.zkt_ecdsa_verify_batch.argtypes = [vp, vp, vp, vp, sz, vp]
+        L.zkt_ecdsa_verify_digest_batch_dev.argtypes = [vp, vp, vp, sz, vp, vp]
         _lib = L
     return _lib
 

@@ -301,3 +301,50 @@ int zkt_hostcheck_group_batch(int grp, int op, const uint32_t* a, const uint32_t
   return 0;
 }
 }  // extern "C"
+
+// ---- SHA-256 and secp256k1 ECDSA (sha256.h, ecdsa.h): the per-message and per-signature functions the kernels of zkt_ecdsa.hip run, on the host ----------------
+#include "ecdsa.h"
+#include "host_abi.h"
+namespace {
+// the generator's comb table in the layout of k_generator_table<SpOps>: [w * 15 + d - 1] = d * 16^w * G, raw Montgomery (x, y)
+const uint32_t* secp_comb_table() {
+  static std::vector<uint32_t> t;
+  if (!t.empty()) return t.data();
+  t.resize((size_t)64 * 15 * 2 * SpC::N);
+  Aff<SpOps> base = PtIO<SpOps>::ld((const uint32_t*)&SECP_GEN);
+  for (int w = 0; w < 64; ++w) {
+    Jac<SpOps> m = jac_from_aff(base);
+    for (int d = 1; d <= 15; ++d) {
+      const Aff<SpOps> a = jac_to_aff(m);
+      uint32_t* e = t.data() + ((size_t)w * 15 + d - 1) * 2 * SpC::N;
+      st_raw<SpC>(e, a.x); st_raw<SpC>(e + SpC::N, a.y);
+      m = jac_add_aff(m, base);
+    }
+    base = jac_to_aff(m);                                           // 16 * base
+  }
+  return t.data();
+}
+}  // namespace
+extern "C" {
+// digest (32 bytes) of msg[0..len) by the padding, block loader and compression the kernels use; msg may have any alignment
+int zkt_hostcheck_sha256(const uint8_t* msg, size_t len, uint8_t* digest) { uint32_t h[8]; sha256_words(msg, len, h); sha256_store_digest(h, digest); return 0; }
+// one compression: h (8 words) updated by the block w (16 big-endian words)
+int zkt_hostcheck_sha256_compress(uint32_t* h, const uint32_t* w) { uint32_t blk[16]; for (int i = 0; i < 16; ++i) blk[i] = w[i]; sha256_compress(h, blk); return 0; }
+// byte `pos` of the padded message of a len-byte msg (pad_msg), and the padded length through *padded_len
+int zkt_hostcheck_sha256_pad(const uint8_t* msg, size_t len, size_t pos, size_t* padded_len) {
+  const uint64_t pl = ((len + 8) / 64 + 1) * 64; if (padded_len) *padded_len = (size_t)pl;
+  return pos < pl ? (int)sha256_padded_byte(msg, len, pl, pos) : -1;
+}
+// ecdsa_verify_one: digest 32 bytes, sig = {r, s} 16 words, pk = one ABI point (18 words); returns 1/0
+int zkt_hostcheck_ecdsa_verify(const uint8_t* digest, const uint32_t* sig, const uint32_t* pk) {
+  uint32_t z[8], tab[ECDSA_TAB * ECDSA_JW];
+  ecdsa_z_from_digest(digest, z);
+  return ecdsa_verify_one<1>(z, sig, sig + 8, pk, secp_comb_table(), tab) ? 1 : 0;
+}
+// ecdsa_sign_one: digest 32 bytes, d and k 8 words each; sig = {r, s} 16 words out; returns the retry flag
+int zkt_hostcheck_ecdsa_sign(const uint8_t* digest, const uint32_t* d, const uint32_t* k, uint32_t* sig) {
+  uint32_t z[8];
+  ecdsa_z_from_digest(digest, z);
+  return ecdsa_sign_one(z, d, k, secp_comb_table(), sig, sig + 8) ? 1 : 0;
+}
+}  // extern "C"

@@ -814,6 +814,128 @@ static int msm_host(int grp, const void* bases, const uint64_t* scalars, size_t 
   return rc;
 }
 
+// ---- SHA-256 and secp256k1 ECDSA (zkt_ecdsa.hip): host-pointer calls staged through the arena on the staging stream ----------------------------------
+namespace {
+// the secp256k1 generator's comb table (built on first use, from a device copy of the generator in g.d_small); caller holds g.mu
+int secp_generator_table(hipStream_t s, const uint32_t** table) {
+  hipError_t e = generator_table(G_SECP, nullptr, table, s);
+  if (e == hipErrorNotReady) {
+    HIPCHK(hipMemcpyAsync(g.d_small, &SECP_GEN, SPB, hipMemcpyHostToDevice, s));
+    e = generator_table(G_SECP, g.d_small, table, s);
+  }
+  HIPCHK(e);
+  return ZKT_OK;
+}
+// bytes of the concatenated messages that the n elements can touch.  As in the BLS calls an element whose end lies before its start is an empty message
+// (the kernels read no byte of it); unlike there, the upload covers the largest offset, so no element reads past it.
+size_t msgs_extent(const uint64_t* offsets, size_t n) {
+  uint64_t m = 0;
+  for (size_t i = 0; i <= n; ++i) m = offsets[i] > m ? offsets[i] : m;
+  return (size_t)m;
+}
+// what one ECDSA call stages: the digests or the messages with their offsets, `a` and `b` (signatures and public keys, or private keys and nonces), the outputs
+struct EcdsaStage { uint8_t *dig = nullptr, *msgs = nullptr; unsigned long long* off = nullptr; uint32_t *a = nullptr, *b = nullptr, *out = nullptr, *flag = nullptr; };
+int ecdsa_stage(const uint8_t* digests, const uint8_t* msgs, const uint64_t* offsets, const void* a, size_t a_bytes, const void* b, size_t b_bytes,
+                size_t out_bytes, size_t n, EcdsaStage& st) {                                      // caller holds g.mu
+  const size_t total = digests ? 0 : msgs_extent(offsets, n);
+  if (total && !msgs) return ZKT_ERR_SHAPE;                      // the extent, not offsets[n]: a non-monotone vector can end at 0 and still name bytes
+  ZCHK(arena_reserve(padded(digests ? n * 32 : total) + padded((n + 1) * 8) + padded(n * a_bytes) + padded(n * b_bytes) + padded(n * out_bytes) + padded(n * 4) + 2048));
+  Carver cv(g.arena);
+  if (digests) { st.dig = cv.take<uint8_t>(n * 32); HIPCHK(hipMemcpyAsync(st.dig, digests, n * 32, hipMemcpyHostToDevice, g.stream)); }
+  else {
+    st.msgs = cv.take<uint8_t>(total); st.off = cv.take<unsigned long long>((n + 1) * 8);
+    if (total) HIPCHK(hipMemcpyAsync(st.msgs, msgs, total, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(st.off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, g.stream));
+  }
+  st.a = cv.take<uint32_t>(n * a_bytes); st.b = cv.take<uint32_t>(n * b_bytes); st.out = cv.take<uint32_t>(n * out_bytes); st.flag = cv.take<uint32_t>(n * 4);
+  if (a_bytes) HIPCHK(hipMemcpyAsync(st.a, a, n * a_bytes, hipMemcpyHostToDevice, g.stream));
+  if (b_bytes) HIPCHK(hipMemcpyAsync(st.b, b, n * b_bytes, hipMemcpyHostToDevice, g.stream));
+  return ZKT_OK;
+}
+int ecdsa_verify_host(const uint8_t* digests, const uint8_t* msgs, const uint64_t* offsets, const zkt_ecdsa_sig* sigs, const zkt_secp_affine* pks, size_t n, uint32_t* ok) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!sigs || !pks || !ok || (digests ? false : (!offsets || (offsets[n] && !msgs)))) return ZKT_ERR_SHAPE;
+  if (n == 0) return ZKT_OK;
+  std::lock_guard<std::mutex> lk(g.mu);
+  EcdsaStage st; const uint32_t* gtab = nullptr;
+  ZCHK(secp_generator_table(g.stream, &gtab));
+  ZCHK(ecdsa_stage(digests, msgs, offsets, sigs, sizeof(zkt_ecdsa_sig), pks, SPB, 4, n, st));
+  HIPCHK(launch_ecdsa_verify(st.dig, st.msgs, st.off, st.a, st.b, gtab, st.out, n, g.stream));
+  HIPCHK(hipMemcpyAsync(ok, st.out, n * 4, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return ZKT_OK;
+}
+int ecdsa_sign_host(const uint8_t* digests, const uint8_t* msgs, const uint64_t* offsets, const uint64_t* sks, const uint64_t* ks, size_t n, zkt_ecdsa_sig* sigs, uint32_t* retry) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!sks || !ks || !sigs || (digests ? false : (!offsets || (offsets[n] && !msgs)))) return ZKT_ERR_SHAPE;
+  if (n == 0) return ZKT_OK;
+  std::vector<uint32_t> own;                                   // a null `retry` is allowed when no element needs one: the flags are still read back
+  if (!retry) { own.resize(n); }
+  uint32_t* flags = retry ? retry : own.data();
+  std::lock_guard<std::mutex> lk(g.mu);
+  EcdsaStage st; const uint32_t* gtab = nullptr;
+  ZCHK(secp_generator_table(g.stream, &gtab));
+  ZCHK(ecdsa_stage(digests, msgs, offsets, sks, FRB, ks, FRB, sizeof(zkt_ecdsa_sig), n, st));
+  HIPCHK(launch_ecdsa_sign(st.dig, st.msgs, st.off, st.a, st.b, gtab, st.out, st.flag, n, g.stream));
+  HIPCHK(hipMemcpyAsync(sigs, st.out, n * sizeof(zkt_ecdsa_sig), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(flags, st.flag, n * 4, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  if (!retry) for (size_t i = 0; i < n; ++i) if (flags[i]) { t_err_index = i; return ZKT_ERR_SHAPE; }
+  return ZKT_OK;
+}
+}  // namespace
+int zkt_sha256_batch(const uint8_t* msgs, const uint64_t* offsets, size_t n, uint8_t* digests) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!offsets || !digests || (offsets[n] && !msgs)) return ZKT_ERR_SHAPE;
+  if (n == 0) return ZKT_OK;
+  std::lock_guard<std::mutex> lk(g.mu);
+  EcdsaStage st;
+  ZCHK(ecdsa_stage(nullptr, msgs, offsets, nullptr, 0, nullptr, 0, 32, n, st));
+  HIPCHK(launch_sha256(st.msgs, st.off, n, (uint8_t*)st.out, g.stream));
+  HIPCHK(hipMemcpyAsync(digests, st.out, n * 32, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return ZKT_OK;
+}
+int zkt_ecdsa_public_keys_batch(const uint64_t* sks, size_t n, zkt_secp_affine* pks) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!sks || !pks) return ZKT_ERR_SHAPE;
+  if (n == 0) return ZKT_OK;
+  std::lock_guard<std::mutex> lk(g.mu);
+  ZCHK(arena_reserve(padded(n * FRB) + padded(n * SPB) + 1024));
+  Carver cv(g.arena);
+  uint32_t* dk = cv.take<uint32_t>(n * FRB); uint32_t* dp = cv.take<uint32_t>(n * SPB);
+  HIPCHK(hipMemcpyAsync(dk, sks, n * FRB, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(g.d_small, &SECP_GEN, SPB, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(launch_generator_mul(G_SECP, g.d_small, dk, dp, n, g.stream));                      // any 256-bit sk: (sk mod n) G and sk G are the same group element
+  HIPCHK(hipMemcpyAsync(pks, dp, n * SPB, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return ZKT_OK;
+}
+int zkt_ecdsa_sign_digest_batch(const uint8_t* digests, const uint64_t* sks, const uint64_t* ks, size_t n, zkt_ecdsa_sig* sigs, uint32_t* retry) {
+  if (!digests) return ensure_ready() != ZKT_OK ? ZKT_ERR_DEVICE : ZKT_ERR_SHAPE;
+  return ecdsa_sign_host(digests, nullptr, nullptr, sks, ks, n, sigs, retry);
+}
+int zkt_ecdsa_sign_batch(const uint8_t* msgs, const uint64_t* offsets, const uint64_t* sks, const uint64_t* ks, size_t n, zkt_ecdsa_sig* sigs, uint32_t* retry) {
+  return ecdsa_sign_host(nullptr, msgs, offsets, sks, ks, n, sigs, retry);
+}
+int zkt_ecdsa_verify_digest_batch(const uint8_t* digests, const zkt_ecdsa_sig* sigs, const zkt_secp_affine* pks, size_t n, uint32_t* ok) {
+  if (!digests) return ensure_ready() != ZKT_OK ? ZKT_ERR_DEVICE : ZKT_ERR_SHAPE;
+  return ecdsa_verify_host(digests, nullptr, nullptr, sigs, pks, n, ok);
+}
+int zkt_ecdsa_verify_batch(const uint8_t* msgs, const uint64_t* offsets, const zkt_ecdsa_sig* sigs, const zkt_secp_affine* pks, size_t n, uint32_t* ok) {
+  return ecdsa_verify_host(nullptr, msgs, offsets, sigs, pks, n, ok);
+}
+// device pointers, ordered on the caller's stream: nothing is staged and nothing waits (the first call of a process builds the generator's table on that stream and waits for it)
+int zkt_ecdsa_verify_digest_batch_dev(const uint8_t* dev_digests, const zkt_ecdsa_sig* dev_sigs, const zkt_secp_affine* dev_pks, size_t n, uint32_t* dev_ok, void* stream) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!dev_digests || !dev_sigs || !dev_pks || !dev_ok) return ZKT_ERR_SHAPE;
+  if (n == 0) return ZKT_OK;
+  const uint32_t* gtab = nullptr;
+  { std::lock_guard<std::mutex> lk(g.mu); ZCHK(secp_generator_table((hipStream_t)stream, &gtab)); }
+  HIPCHK(launch_ecdsa_verify(dev_digests, nullptr, nullptr, (const uint32_t*)dev_sigs, (const uint32_t*)dev_pks, gtab, dev_ok, n, (hipStream_t)stream));
+  return ZKT_OK;
+}
+
 #define ZKT_BASES_API(NAME, GRP, PT)                                                                                             \
   int zkt_##NAME##_bases_from_device(const PT* dev, size_t n, void* stream, zkt_##NAME##_bases** out) {                          \
     return bases_from_device(GRP, dev, n, stream, (zkt_bases_impl**)out); }                                                     \

@@ -188,30 +188,42 @@ __global__ void __launch_bounds__(64) k_generator_mul(const uint32_t* __restrict
 }
 namespace {
 struct GeneratorTable { std::mutex mu; uint32_t* dev = nullptr; };
-GeneratorTable g_gen_table[2];                                     // G_G1, G_G2
+GeneratorTable g_gen_table[3];                                     // G_G1, G_G2, G_SECP
 }
 // zkt_shutdown: the comb tables live on the device zkt_init chose; a later zkt_init may pick another one, so they are rebuilt on first use
 void group_release_device_state() {
   for (GeneratorTable& T : g_gen_table) { std::lock_guard<std::mutex> lk(T.mu); if (T.dev) { (void)hipFree(T.dev); T.dev = nullptr; } }
 }
-hipError_t launch_generator_mul(int grp, const uint32_t* gen_abi, const uint32_t* k, uint32_t* out, size_t n, hipStream_t s) {
-  if (grp != G_G1 && grp != G_G2) return hipErrorInvalidValue;
-  if (n == 0) return hipSuccess;
-  GeneratorTable& T = g_gen_table[grp == G_G1 ? 0 : 1];
-  {
-    std::lock_guard<std::mutex> lk(T.mu);
-    if (!T.dev) {                                                  // first use in this process: build on the caller's stream and wait, so that later callers on other streams find it complete
-      const size_t bytes = (size_t)COMB_ENTRIES * 2 * (grp == G_G1 ? RawXY<FqOps>::CW : RawXY<Fq2Ops>::CW) * 4;
-      uint32_t* mem = nullptr; hipError_t e;
-      if ((e = hipMalloc((void**)&mem, bytes)) != hipSuccess) return e;
-      if (grp == G_G1) hipLaunchKernelGGL(k_generator_table<FqOps>, dim3(COMB_ENTRIES / 64), dim3(64), 0, s, gen_abi, mem);
-      else hipLaunchKernelGGL(k_generator_table<Fq2Ops>, dim3(COMB_ENTRIES / 64), dim3(64), 0, s, gen_abi, mem);
-      if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(s)) != hipSuccess) { (void)hipFree(mem); return e; }
-      T.dev = mem;
-    }
+template <class F> static hipError_t generator_table_build(const uint32_t* gen_abi, uint32_t** out, hipStream_t s) {
+  uint32_t* mem = nullptr; hipError_t e;
+  if ((e = hipMalloc((void**)&mem, (size_t)COMB_ENTRIES * 2 * RawXY<F>::CW * 4)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_generator_table<F>, dim3(COMB_ENTRIES / 64), dim3(64), 0, s, gen_abi, mem);
+  if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(s)) != hipSuccess) { (void)hipFree(mem); return e; }
+  *out = mem;
+  return hipSuccess;
+}
+hipError_t generator_table(int grp, const uint32_t* gen_abi, const uint32_t** table, hipStream_t s) {
+  if (grp != G_G1 && grp != G_G2 && grp != G_SECP) return hipErrorInvalidValue;
+  GeneratorTable& T = g_gen_table[grp];
+  std::lock_guard<std::mutex> lk(T.mu);
+  if (!T.dev && !gen_abi) return hipErrorNotReady;                 // a caller that only wants the table if it exists (it then supplies the generator and asks again)
+  if (!T.dev) {                                                    // first use in this process: build on the caller's stream and wait, so that later callers on other streams find it complete
+    const hipError_t e = grp == G_G1 ? generator_table_build<FqOps>(gen_abi, &T.dev, s) : grp == G_G2 ? generator_table_build<Fq2Ops>(gen_abi, &T.dev, s)
+                                                                                                       : generator_table_build<SpOps>(gen_abi, &T.dev, s);
+    if (e != hipSuccess) return e;
   }
-  if (grp == G_G1) hipLaunchKernelGGL(k_generator_mul<FqOps>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, (const uint32_t*)T.dev, k, out, n);
-  else hipLaunchKernelGGL(k_generator_mul<Fq2Ops>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, (const uint32_t*)T.dev, k, out, n);
+  *table = T.dev;
+  return hipSuccess;
+}
+hipError_t launch_generator_mul(int grp, const uint32_t* gen_abi, const uint32_t* k, uint32_t* out, size_t n, hipStream_t s) {
+  if (grp != G_G1 && grp != G_G2 && grp != G_SECP) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  const uint32_t* table = nullptr;
+  const hipError_t e = generator_table(grp, gen_abi, &table, s);
+  if (e != hipSuccess) return e;
+  if (grp == G_G1) hipLaunchKernelGGL(k_generator_mul<FqOps>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, table, k, out, n);
+  else if (grp == G_G2) hipLaunchKernelGGL(k_generator_mul<Fq2Ops>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, table, k, out, n);
+  else hipLaunchKernelGGL(k_generator_mul<SpOps>, dim3(grid_blocks(n, 64)), dim3(64), 0, s, table, k, out, n);
   return hipGetLastError();
 }
 

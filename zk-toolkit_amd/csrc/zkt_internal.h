@@ -62,9 +62,12 @@ struct FixedMul { const uint32_t* table; const uint32_t* k; uint32_t* out; };
 struct FixedMuls { FixedMul m[16]; int n; };
 struct FixedTables { const uint32_t* point[12]; uint32_t* table[12]; int n; };     // up to twelve points per launch, one wave each, side by side
 hipError_t launch_fixed_tables(int grp, const FixedTables& t, hipStream_t s);
-// out[i] = k[i] * G for the group's standard generator (G_G1 / G_G2; gen_abi = that generator on the device, read on first use only): a comb table of
+// out[i] = k[i] * G for the group's standard generator (G_G1 / G_G2 / G_SECP; gen_abi = that generator on the device, read on first use only): a comb table of
 // 960 multiples built once per process, at most 64 mixed additions per product instead of a 255-step double-and-add.  k: 8 words per scalar.
 hipError_t launch_generator_mul(int grp, const uint32_t* gen_abi, const uint32_t* k, uint32_t* out, size_t n, hipStream_t s);
+// the comb table itself, built on first use as above: 960 entries [w * 15 + d - 1] = d * 16^w * G, raw Montgomery (x, y) — for kernels that add generator multiples into a sum of their own.
+// gen_abi == nullptr: hipErrorNotReady unless the table exists already
+hipError_t generator_table(int grp, const uint32_t* gen_abi, const uint32_t** table, hipStream_t s);
 hipError_t launch_fixed_muls(int grp, const FixedMuls& f, hipStream_t s);
 // the same product for a whole batch: out[(j * n + i)] = k[(i * n_pts + j)] * P_j from tables[j] (64 points each), one wave per product, grid = n * n_pts
 hipError_t launch_fixed_muls_batch(int grp, const uint32_t* tables, const uint32_t* k, uint32_t* out, size_t n, int n_pts, hipStream_t s);
@@ -118,6 +121,17 @@ hipError_t launch_short_loop_guards(const PairArgs& a, int K, uint32_t* flags, s
 void group_release_device_state();
 void pairing_release_device_state();
 hipError_t launch_tate(const uint32_t* g1, const uint32_t* g2, uint32_t* out, size_t n, unsigned long long* err, hipStream_t s);
+
+// ---- SHA-256 and secp256k1 ECDSA (zkt_ecdsa.hip) ---------------------------------------------------------------
+// digests[i] = SHA-256(msgs[off[i] .. off[i+1])), 32 bytes each; one lane per message
+hipError_t launch_sha256(const uint8_t* msgs, const unsigned long long* off, size_t n, uint8_t* digests, hipStream_t s);
+// Ecdsa::verify, one lane per signature.  Exactly one of (digests) and (msgs, off) is given: with messages the lane hashes its own first.
+// sigs: n x 16 words {r, s}; pks: n ABI points; gtab: generator_table(G_SECP)
+hipError_t launch_ecdsa_verify(const uint8_t* digests, const uint8_t* msgs, const unsigned long long* off, const uint32_t* sigs, const uint32_t* pks,
+                               const uint32_t* gtab, uint32_t* ok, size_t n, hipStream_t s);
+// Ecdsa::sign with the nonce given; retry[i] = 1 and sigs[i] = 0 where the reference would draw another nonce.  sks, ks: n x 8 words, reduced mod n on load
+hipError_t launch_ecdsa_sign(const uint8_t* digests, const uint8_t* msgs, const unsigned long long* off, const uint32_t* sks, const uint32_t* ks,
+                             const uint32_t* gtab, uint32_t* sigs, uint32_t* retry, size_t n, hipStream_t s);
 
 // ---- MSM (zkt_msm.hip), generic over the group (G_G1, G_G2, G_SECP) ------------------------------------------
 struct MsmPlan {
