@@ -6,10 +6,10 @@ bucket of its set and vector v + 1 starts in the first bucket of the next" and h
 import numpy as np
 import msm_plan_model as M
 
-# ---- limits, each restating one line of include/zkt.h or zkt_api.cpp ----------------------------------------------------------------
+# ---- limits, each restating one line of include/zkt.h or zkt_msm_handle.cpp ----------------------------------------------------------------
 BATCH_MAX = 32                       # include/zkt.h, `#define ZKT_MSM_BATCH_MAX 32`
 BATCH_MAX_TERMS = 1 << 22            # include/zkt.h, `#define ZKT_MSM_BATCH_MAX_TERMS ((size_t)1 << 22)`: k * n of one batch
-BATCH_MAX_N = 1 << 19                # zkt_api.cpp, msm_batch_submit_locked `n >= (size_t(1) << 19)` is refused: one MSM fills the chip there
+BATCH_MAX_N = 1 << 19                # zkt_msm_handle.cpp, msm_batch_submit `n >= (size_t(1) << 19)` is refused: one MSM fills the chip there
 GROUPS = M.GROUPS
 FUNCTIONS = tuple(f"zkt_{g}_msm_batch_{f}" for g in GROUPS for f in ("submit", "collect", "dev"))
 

@@ -17,7 +17,7 @@ BULK_MIN = 4 * RED_NG       # msm_reduce_coop.h, coop_block_sum `bulk = count > 
 PART_MIN_ENTRIES = 1 << 22  # zkt_msm.hip, launch_msm_sort `partition = (size_t)P.nwin * n >= (size_t(1) << 22)`
 PART_LO, PART_TPB, PART_CHUNK = 9, 256, 8192       # zkt_msm.hip, `PART_LO = 9, PART_SUB = 1 << PART_LO, PART_TPB = 256, PART_TILE = 4 * PART_TPB, PART_CHUNK = 8192, PART_MAXP = 2048`
 PART_SUB, PART_TILE, PART_MAXP = 1 << PART_LO, 4 * PART_TPB, 2048
-GRAPH_MAX_N = 1 << 19       # zkt_api.cpp, msm_submit_locked `small = h->n < (size_t(1) << 19)`: a small resident set replays a captured graph
+GRAPH_MAX_N = 1 << 19       # zkt_msm_handle.cpp, msm_submit `small = h.n < (size_t(1) << 19)`: a small resident set replays a captured graph
 CHUNK_MIN, CHUNK_MAX = 8, 128                       # zkt_msm.hip, pick_chunk: clamp to [8, MSM_CHUNK_MAX = 128]
 TASK_LANES = {"g1": 196608, "secp": 196608, "g2": 65536}   # pick_chunk `tasks = grp == G_G2 ? 65536 : 196608`
 COORD_WORDS = {"g1": 14, "g2": 28, "secp": 8}      # zkt_msm.hip coord_words(): FqC::N = 14 limbs of 28 bits (zkt_constants.h), Fq2 twice that, SpC::N = 8
@@ -85,7 +85,7 @@ def plan(n, group, form):
 
 
 def g1_resident_workspace_bytes(n):
-    """zkt_g1_msm_workspace_bytes(n) (zkt_api.cpp): one slot's workspace plus `nwin * n * 97` bytes for the window-multiple table"""
+    """zkt_g1_msm_workspace_bytes(n) (zkt_msm_handle.cpp): one slot's workspace plus `nwin * n * 97` bytes for the window-multiple table"""
     p = plan(n, "g1", "resident")
     return p["ws_bytes"] + p["nwin"] * n * 97
 

@@ -1,4 +1,4 @@
-// Host-side plumbing shared by the translation units that implement the C ABI (zkt_api.cpp, zkt_comm.cpp, zkt_protocols.hip,
+// Host-side plumbing shared by the translation units that implement the C ABI (zkt_api.cpp, zkt_msm_handle.cpp, zkt_comm.cpp, zkt_protocols.hip,
 // zkt_pinocchio.hip, zkt_groth16_r1cs.hip): the HIP-error check, an owning device buffer, the ABI point sizes and the generators.
 // Host code only: no device header includes this file.
 #pragma once
@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <cstdio>
+#include <cstdlib>
 #include "../../include/zkt.h"
 #include "zkt_internal.h"
 
@@ -43,6 +44,11 @@ inline int down(void* h, const void* d, size_t bytes, hipStream_t s) { if (bytes
 // ABI sizes (include/zkt.h)
 constexpr size_t G1B = sizeof(zkt_g1_affine), G2B = sizeof(zkt_g2_affine), SPB = sizeof(zkt_secp_affine), FRB = 32;
 inline size_t abi_pt_bytes(int grp) { return grp == G_G1 ? G1B : grp == G_G2 ? G2B : SPB; }
+// one internal (Montgomery) coordinate of a group's points: a third of a Jacobian partial (zkt_api.cpp asserts ZKT_*_PARTIAL_WORDS against the limb layout)
+inline size_t grp_coord_bytes(int grp) { return 4 * (grp == G_G1 ? ZKT_G1_PARTIAL_WORDS : grp == G_G2 ? ZKT_G2_PARTIAL_WORDS : ZKT_SECP_PARTIAL_WORDS) / 3; }
+// ZKT_DEBUG_POISON=1: every MSM workspace is filled with a garbage pattern when it is allocated, so a kernel that reads a word nobody wrote gets 0xA5A5A5A5
+// instead of the zeros a fresh allocation happens to hold (tools/diag/msm_repeat.py and the MSM tests are run this way).
+inline bool debug_poison() { static const bool on = [] { const char* e = getenv("ZKT_DEBUG_POISON"); return e && *e == '1'; }(); return on; }
 
 // a 4-limb value that is 0 mod r: 0, r or 2r (3r > 2^256).  Values are reduced on load, so a trapdoor must pass this test, not a test of its raw limbs.
 inline bool fr_is_zero_mod_r(const uint64_t* a) {

@@ -1,6 +1,7 @@
 // C ABI (include/zkt.h) over the HIP kernels.  Host-pointer entry points stage through
 // a grow-only device arena; `_dev` entry points launch on the caller's stream.  There is
 // no CPU compute path in this file: without a device every entry point fails.
+// The resident-base MSM handle (zkt_*_bases_*, zkt_*_msm_submit / _collect / _dev, zkt_*_msm_batch_*) is zkt_msm_handle.cpp.
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <vector>
@@ -149,87 +150,11 @@ int tower_batch(int deg, int op, const uint64_t* a, const uint64_t* b, uint64_t*
 
 }  // namespace
 
-static constexpr int MSM_SLOTS = 8;
-struct MsmSlot {                      // one in-flight MSM: workspace, result buffers, stage events
-  hipEvent_t e_in = nullptr, e_sorted = nullptr, e_acc0 = nullptr, e_acc1 = nullptr, e_done = nullptr;
-  void* workspace = nullptr;
-  uint32_t* d_result_jac = nullptr;   // 3 coordinates (Jacobian partial)
-  uint32_t* d_out_abi = nullptr;      // one ABI point
-  uint8_t* h_out = nullptr;           // pinned, one ABI point
-  bool busy = false;
-  // graph replay of a small MSM's pipeline (msm_submit_locked): executable graphs captured on this slot, keyed by the scalar vector's address
-  static constexpr int NGRAPH = 4;
-  hipGraphExec_t gexec[NGRAPH] = {}; const void* gkey[NGRAPH] = {}; unsigned gnext = 0; bool timed = false;
-};
-struct MsmBatch {                     // the one in-flight batch of a handle (zkt_*_msm_batch_*): independent of the slots, created on the first batch
-  hipEvent_t e_in = nullptr, e_done = nullptr;
-  void* workspace = nullptr;          // msm_plan_batch(n, grp, cap).ws_bytes: grown when a later batch has more vectors
-  uint32_t* d_jac = nullptr;          // cap Jacobian partials, 3 coordinates each
-  uint32_t* d_abi = nullptr;          // cap ABI points
-  uint8_t* h_out = nullptr;           // pinned, cap ABI points
-  int cap = 0, k = 0;                 // vectors the buffers hold / vectors of the batch in flight
-  bool busy = false;
-};
-struct zkt_bases_impl {               // one resident base set of any group; zkt_g1_bases / zkt_g2_bases / zkt_secp_bases are this
-  size_t n = 0;
-  int grp = G_G1;
-  MsmPlan plan{};
-  uint32_t* table = nullptr;     // nwin*n affine points, 2 internal coordinates each
-  uint8_t* inf = nullptr;        // nwin*n flags
-  // software pipeline: the three stages of consecutive MSMs run on three streams (sort | accumulate | reduce),
-  // chained by events, so the atomic-bound sort and the latency-bound reduce of neighbours hide under the
-  // VALU-bound accumulation of the current one.
-  static constexpr int GROUP_TAILS = 4;   // reduce streams of a group of sets that share their streams (zkt_internal_bases_share_streams)
-  static constexpr int NTAIL = 8;   // reduce chains of alternate MSMs run side by side: each is latency-bound, not throughput-bound (large MSMs use two of them)
-  hipStream_t s_sort = nullptr, s_acc = nullptr, s_tail[NTAIL] = {};
-  // a group of base sets that always work on the same job (the four sets of a Groth16 key) shares ONE set of streams: every stream beyond the
-  // hardware queues (8) is folded onto a queue that already carries another stream, and a sort queued behind someone else's reduce chain waits for it
-  // (measured: the A sum of a proof started 16 ms late behind the C1 reduce, profiles/r03_groth16_timeline.txt)
-  bool own_streams = true, acc_owned = false, grouped = false; int tail_base = 0, tail_span = 0;
-  MsmSlot slot[MSM_SLOTS];
-  MsmBatch batch;
-  std::mutex mu;                 // slot state: calls on one handle are serialised (submit/collect of different slots may come from different threads)
-};
-struct zkt_g1_bases : zkt_bases_impl {};
-struct zkt_g2_bases : zkt_bases_impl {};
-struct zkt_secp_bases : zkt_bases_impl {};
-static size_t grp_coord_bytes(int grp) { return 4 * (grp == G_G1 ? zkt::FqC::N : grp == G_G2 ? 2 * zkt::FqC::N : zkt::SpC::N); }   // internal (Montgomery) coordinate
-static int streams_ready(zkt_bases_impl* h) {
-  if (h->grouped || !h->own_streams || (h->s_acc && h->s_sort && h->s_tail[zkt_bases_impl::NTAIL - 1])) return ZKT_OK;
-  int lo = 0, hi = 0;
-  HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));        // hi = numerically smallest = highest priority
-  if (!h->s_sort) HIPCHK(hipStreamCreateWithPriority(&h->s_sort, hipStreamNonBlocking, hi));
-  if (!h->s_acc) HIPCHK(hipStreamCreateWithPriority(&h->s_acc, hipStreamNonBlocking, lo));
-  for (int k = 0; k < zkt_bases_impl::NTAIL; ++k) if (!h->s_tail[k]) HIPCHK(hipStreamCreateWithPriority(&h->s_tail[k], hipStreamNonBlocking, hi));
-  return ZKT_OK;
-}
-// ZKT_DEBUG_POISON=1: every MSM workspace is filled with a garbage pattern when it is allocated, so a kernel that reads a word nobody wrote gets 0xA5A5A5A5
-// instead of the zeros a fresh allocation happens to hold (tools/diag/msm_repeat.py and the MSM tests are run this way).
-static bool debug_poison() { static const bool on = [] { const char* e = getenv("ZKT_DEBUG_POISON"); return e && *e == '1'; }(); return on; }
-// The pipeline of an MSM below 2^19 terms is replayed as one graph launch per submit (msm_submit_locked); ZKT_MSM_GRAPH=0 issues its launches one by one instead.
-// Round 2 took this out because the 65,536-bit range-proof test aborted; round 3 found why (tools/diag/rp_graph.py): the captured graph held runtime-owned nodes — the
-// hipMemsetAsync of the counters and the copy of the result — and replaying such a graph after ANY later hipFree in the process (a torch cache flush, a second context
-// freeing its build scratch) ended in a memory access fault.  With kernel nodes only (k_zero_words clears the counters, the copy follows the graph on the stream) the
-// replay survives all of that: every variant of the diagnostic, and the whole GPU suite, run in this mode.
-static bool msm_graphs() { static const bool on = [] { const char* e = getenv("ZKT_MSM_GRAPH"); return !(e && *e == '0'); }(); return on; }
-static int slot_ready(zkt_bases_impl* h, int k) {   // lazily create the slot's workspace
-  int rc = streams_ready(h); if (rc) return rc;
-  MsmSlot& S = h->slot[k];
-  if (S.workspace) return ZKT_OK;
-  HIPCHK(hipEventCreateWithFlags(&S.e_in, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&S.e_sorted, hipEventDisableTiming));
-  HIPCHK(hipEventCreate(&S.e_acc0)); HIPCHK(hipEventCreate(&S.e_acc1)); HIPCHK(hipEventCreateWithFlags(&S.e_done, hipEventDisableTiming));
-  HIPCHK(hipMalloc(&S.workspace, h->plan.ws_bytes));
-  if (debug_poison()) { HIPCHK(hipMemset(S.workspace, 0xA5, h->plan.ws_bytes)); HIPCHK(hipDeviceSynchronize()); }
-  HIPCHK(hipMalloc((void**)&S.d_result_jac, 3 * grp_coord_bytes(h->grp)));
-  HIPCHK(hipMalloc((void**)&S.d_out_abi, abi_pt_bytes(h->grp)));
-  HIPCHK(hipHostMalloc((void**)&S.h_out, abi_pt_bytes(h->grp), hipHostMallocDefault));
-  return ZKT_OK;
-}
-
 int zkt_internal_ready() { return ensure_ready(); }
 hipStream_t zkt_internal_stream() { return g.stream; }
 int zkt_internal_device() { return g.device; }
 void zkt_internal_set_error_index(size_t i) { t_err_index = i; }
+void zkt_internal_set_last_kernel(float ms, const char* name) { t_kernel_ms = ms; t_kernel_name = name; }
 
 extern "C" {
 
@@ -508,270 +433,6 @@ int zkt_tate_batch_dev(const zkt_g1_affine* g1, const zkt_g2_affine* g2, uint64_
   return rc;
 }
 
-static int bases_build(zkt_bases_impl* h, const uint32_t* dev_abi, hipStream_t s) {
-  const size_t n = h->n;
-  h->plan = msm_plan(n, h->grp);
-  const size_t tot = (size_t)h->plan.nwin * (n ? n : 1);
-  HIPCHK(hipMalloc((void**)&h->table, tot * 2 * grp_coord_bytes(h->grp)));
-  HIPCHK(hipMalloc((void**)&h->inf, tot));
-  HIPCHK(launch_msm_to_kernel_layout(h->grp, dev_abi, h->table, h->inf, n, s));
-  uint32_t* tmp = nullptr;                                   // Z and prefix products of the per-lane batched normalisation
-  if (h->plan.nwin > 1) HIPCHK(hipMalloc((void**)&tmp, (size_t)(h->plan.nwin - 1) * (n ? n : 1) * 2 * grp_coord_bytes(h->grp)));
-  hipError_t e = launch_msm_precompute(h->grp, h->table, h->inf, n, h->plan.c, h->plan.nwin, tmp, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (tmp) hipFree(tmp);
-  HIPCHK(e);
-  return ZKT_OK;
-}
-static void batch_release(MsmBatch& Bt) {
-  if (Bt.workspace) hipFree(Bt.workspace); if (Bt.d_jac) hipFree(Bt.d_jac); if (Bt.d_abi) hipFree(Bt.d_abi);
-  if (Bt.h_out) hipHostFree(Bt.h_out);
-  Bt.workspace = nullptr; Bt.d_jac = Bt.d_abi = nullptr; Bt.h_out = nullptr; Bt.cap = 0;
-}
-static void bases_free(zkt_bases_impl* h) {
-  if (!h) return;
-  if (h->batch.busy && h->batch.e_done) hipEventSynchronize(h->batch.e_done);      // a batch in flight reads the table
-  if (h->table) hipFree(h->table);
-  if (h->inf) hipFree(h->inf);
-  if (h->own_streams) {
-    for (hipStream_t st : {h->s_sort, h->s_acc}) if (st) { hipStreamSynchronize(st); hipStreamDestroy(st); }
-    for (hipStream_t st : h->s_tail) if (st) { hipStreamSynchronize(st); hipStreamDestroy(st); }
-  } else {                                     // borrowed streams: wait for this set's own work, leave them to their owner (freed after the borrowers)
-    for (hipStream_t st : {h->s_sort, h->s_acc}) if (st) hipStreamSynchronize(st);
-    for (hipStream_t st : h->s_tail) if (st) hipStreamSynchronize(st);
-    if (h->acc_owned && h->s_acc) hipStreamDestroy(h->s_acc);
-  }
-  for (MsmSlot& S : h->slot) {
-    for (hipEvent_t ev : {S.e_in, S.e_sorted, S.e_acc0, S.e_acc1, S.e_done}) if (ev) hipEventDestroy(ev);
-    for (hipGraphExec_t& ge : S.gexec) if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
-    if (S.workspace) hipFree(S.workspace); if (S.d_result_jac) hipFree(S.d_result_jac); if (S.d_out_abi) hipFree(S.d_out_abi);
-    if (S.h_out) hipHostFree(S.h_out);
-  }
-  for (hipEvent_t ev : {h->batch.e_in, h->batch.e_done}) if (ev) hipEventDestroy(ev);
-  batch_release(h->batch);
-  delete h;
-}
-static int bases_from_device(int grp, const void* dev_bases, size_t n, void* stream, zkt_bases_impl** out) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!out || (n && !dev_bases) || n >= (size_t(1) << 26)) return ZKT_ERR_SHAPE;
-  zkt_bases_impl* h = new zkt_bases_impl(); h->n = n; h->grp = grp;
-  int rc = bases_build(h, (const uint32_t*)dev_bases, (hipStream_t)stream);
-  if (rc) { bases_free(h); return rc; }
-  *out = h; return ZKT_OK;
-}
-static int bases_upload(int grp, const void* host, size_t n, zkt_bases_impl** out) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!out || (n && !host)) return ZKT_ERR_SHAPE;
-  HIPCHK(hipSetDevice(g.device));
-  uint32_t* tmp = nullptr;
-  HIPCHK(hipMalloc((void**)&tmp, (n ? n : 1) * abi_pt_bytes(grp)));
-  if (n) HIPCHK(hipMemcpy(tmp, host, n * abi_pt_bytes(grp), hipMemcpyHostToDevice));
-  int rc = bases_from_device(grp, tmp, n, g.stream, out);
-  hipFree(tmp);
-  return rc;
-}
-static hipStream_t slot_tail_stream(zkt_bases_impl* h, int slot) {
-  if (h->grouped) return h->s_tail[(h->tail_base + slot % h->tail_span) % zkt_bases_impl::GROUP_TAILS];      // a span may wrap around the group's four reduce streams
-  const bool small = h->n < (size_t(1) << 19);
-  return h->s_tail[small ? slot % zkt_bases_impl::NTAIL : slot % 2];
-}
-// caller holds h->mu
-static int msm_submit_locked(zkt_bases_impl* h, const uint64_t* dev_scalars, size_t n, void* stream, int slot) {
-  if (n != h->n || (n && !dev_scalars) || slot < 0 || slot >= MSM_SLOTS) return ZKT_ERR_SHAPE;
-  if (h->slot[slot].busy) return ZKT_ERR_SHAPE;          // collect it first
-  int rc = slot_ready(h, slot); if (rc) return rc;
-  MsmSlot& S = h->slot[slot];
-  // inputs are produced on the caller's stream: order the sort stage behind it
-  HIPCHK(hipEventRecord(S.e_in, (hipStream_t)stream));
-  const bool small = h->n < (size_t(1) << 19);       // (a set that shares a key's streams runs on the group's reduce stream for this slot: slot_tail_stream)
-  hipStream_t st = slot_tail_stream(h, slot);
-  hipStream_t ss = small ? st : h->s_sort;
-  HIPCHK(hipStreamWaitEvent(ss, S.e_in, 0));
-  if (small && msm_graphs()) {
-    // A small MSM is ~20 launches of a few microseconds of GPU time each: the protocols that run several of them side by side (a range proof's five, a Pinocchio proof's
-    // ten) are bound by the rate at which the host can submit them.  The whole pipeline of a slot — memsets, sort, accumulate, reduce, the copy of the result — touches only
-    // the slot's own buffers and the scalar vector (kernel launches only: the counters are cleared by a kernel of the pipeline's own), so it is captured ONCE per (slot, scalar address) on the slot's stream and replayed as one graph launch.  Nothing inside
-    // the capture waits on or records an event (the input dependency is the stream wait above, completion is e_done below); the slot is not busy here, so no launch of an
-    // executable graph that gets evicted is still in flight.
-    int hit = -1;
-    for (int k = 0; k < MsmSlot::NGRAPH; ++k) if (S.gexec[k] && S.gkey[k] == (const void*)dev_scalars) hit = k;
-    if (hit < 0) {
-      hit = (int)(S.gnext++ % MsmSlot::NGRAPH);
-      if (S.gexec[hit]) { (void)hipGraphExecDestroy(S.gexec[hit]); S.gexec[hit] = nullptr; }
-      hipGraph_t graph = nullptr;
-      HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-      hipError_t e = launch_msm_sort(h->plan, h->inf, (const uint32_t*)dev_scalars, S.workspace, st);
-      if (e == hipSuccess) e = launch_msm_accumulate(h->plan, h->table, S.workspace, st);
-      if (e == hipSuccess) e = launch_msm_reduce(h->plan, S.workspace, S.d_result_jac, S.d_out_abi, st);
-      const hipError_t e2 = hipStreamEndCapture(st, &graph);                 // always: the stream must leave capture mode
-      if (e != hipSuccess || e2 != hipSuccess || !graph) { if (graph) (void)hipGraphDestroy(graph); HIPCHK(e != hipSuccess ? e : (e2 != hipSuccess ? e2 : hipErrorUnknown)); }
-      e = hipGraphInstantiate(&S.gexec[hit], graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (e != hipSuccess) { S.gexec[hit] = nullptr; HIPCHK(e); }
-      S.gkey[hit] = (const void*)dev_scalars;
-    }
-    HIPCHK(hipGraphLaunch(S.gexec[hit], st));
-    HIPCHK(hipMemcpyAsync(S.h_out, S.d_out_abi, abi_pt_bytes(h->grp), hipMemcpyDeviceToHost, st));      // kernels only inside the graph: the copy of the result follows it on the stream
-    HIPCHK(hipEventRecord(S.e_done, st));
-    S.timed = false; S.busy = true;
-    return ZKT_OK;
-  }
-  S.timed = true;
-  HIPCHK(launch_msm_sort(h->plan, h->inf, (const uint32_t*)dev_scalars, S.workspace, ss));
-  HIPCHK(hipEventRecord(S.e_sorted, ss));
-  // a large MSM fills the chip, so its stages queue on per-stage streams (sort of MSM k+1 under the accumulation of MSM k); below 2^19 terms every
-  // stage is a latency-bound sliver of the chip (one short wave per SIMD), so each slot runs its whole MSM on its own stream, side by side with the others
-  hipStream_t sa = small ? st : h->s_acc;
-  HIPCHK(hipStreamWaitEvent(sa, S.e_sorted, 0));
-  HIPCHK(hipEventRecord(S.e_acc0, sa));
-  HIPCHK(launch_msm_accumulate(h->plan, h->table, S.workspace, sa));
-  HIPCHK(hipEventRecord(S.e_acc1, sa));
-  HIPCHK(hipStreamWaitEvent(st, S.e_acc1, 0));
-  HIPCHK(launch_msm_reduce(h->plan, S.workspace, S.d_result_jac, S.d_out_abi, st));
-  HIPCHK(hipMemcpyAsync(S.h_out, S.d_out_abi, abi_pt_bytes(h->grp), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipEventRecord(S.e_done, st));
-  S.busy = true;
-  return ZKT_OK;
-}
-static int msm_collect_locked(zkt_bases_impl* h, int slot, void* out, uint32_t* dev_partial_jac) {
-  if (slot < 0 || slot >= MSM_SLOTS || !h->slot[slot].busy) return ZKT_ERR_SHAPE;
-  MsmSlot& S = h->slot[slot];
-  HIPCHK(hipEventSynchronize(S.e_done));
-  if (dev_partial_jac) {        // copied on the slot's own tail stream and waited for: complete when this returns, and never overtaken by a re-submit of the slot
-    hipStream_t st = slot_tail_stream(h, slot);
-    HIPCHK(hipMemcpyAsync(dev_partial_jac, S.d_result_jac, 3 * grp_coord_bytes(h->grp), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  if (out) memcpy(out, S.h_out, abi_pt_bytes(h->grp));
-  float ms = 0.f;
-  if (S.timed && hipEventElapsedTime(&ms, S.e_acc0, S.e_acc1) == hipSuccess) { t_kernel_ms = ms; t_kernel_name = "k_accumulate"; }
-  else { t_kernel_ms = 0.f; t_kernel_name = "msm_graph"; }      // a graph-replayed MSM carries no per-kernel events: say so instead of leaving the previous operation's figures
-  S.busy = false;
-  return ZKT_OK;
-}
-static int msm_submit(zkt_bases_impl* h, const uint64_t* dev_scalars, size_t n, void* stream, int slot) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!h) return ZKT_ERR_SHAPE;
-  std::lock_guard<std::mutex> lk(h->mu);
-  return msm_submit_locked(h, dev_scalars, n, stream, slot);
-}
-static int msm_collect(zkt_bases_impl* h, int slot, void* out, uint32_t* dev_partial_jac) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!h) return ZKT_ERR_SHAPE;
-  std::lock_guard<std::mutex> lk(h->mu);
-  return msm_collect_locked(h, slot, out, dev_partial_jac);
-}
-// blocking form: slot 0, submit + collect under one hold of the handle's lock (two threads may share a handle)
-static int msm_dev(zkt_bases_impl* h, const uint64_t* dev_scalars, size_t n, void* stream, void* out, uint32_t* dev_partial_jac) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!h || (!out && !dev_partial_jac)) return ZKT_ERR_SHAPE;
-  std::lock_guard<std::mutex> lk(h->mu);
-  int rc = msm_submit_locked(h, dev_scalars, n, stream, 0);
-  if (rc) return rc;
-  return msm_collect_locked(h, 0, out, dev_partial_jac);
-}
-// ---- batched form: k scalar vectors over the handle's base set in ONE pipeline (msm_plan_batch) -------------------------------------------------
-// Below 2^19 terms every kernel of an MSM is a latency-bound sliver of the chip, and k MSMs on k slots are k chains of ~20 such kernels side by side.  The batch
-// runs ONE chain whose grids cover all k vectors: bucket set v for vector v, one task list, one accumulate launch, the reduce kernels with grid.y = k.
-// It has a workspace, result buffers and a completion event of its own, so slot MSMs and a batch may be in flight on one handle together; it runs on the reduce
-// stream of the last slot (a grouped handle: the group's stream for that slot), issued launch by launch — no graph (profiles/msm_batch_go_no_go.md).
-static hipStream_t batch_stream(zkt_bases_impl* h) { return slot_tail_stream(h, MSM_SLOTS - 1); }
-static int batch_ready(zkt_bases_impl* h, int k) {      // buffers for k vectors: allocates on the first batch and when k exceeds every earlier one
-  int rc = streams_ready(h); if (rc) return rc;
-  MsmBatch& Bt = h->batch;
-  if (!Bt.e_in) HIPCHK(hipEventCreateWithFlags(&Bt.e_in, hipEventDisableTiming));
-  if (!Bt.e_done) HIPCHK(hipEventCreateWithFlags(&Bt.e_done, hipEventDisableTiming));
-  if (k <= Bt.cap) return ZKT_OK;
-  HIPCHK(hipStreamSynchronize(batch_stream(h)));         // nothing of an earlier (collected) batch is still queued on the buffers about to go
-  batch_release(Bt);
-  const size_t wsb = msm_plan_batch(h->n, h->grp, k).ws_bytes, ptb = abi_pt_bytes(h->grp);
-  HIPCHK(hipMalloc(&Bt.workspace, wsb));
-  if (debug_poison()) { HIPCHK(hipMemset(Bt.workspace, 0xA5, wsb)); HIPCHK(hipDeviceSynchronize()); }
-  HIPCHK(hipMalloc((void**)&Bt.d_jac, (size_t)k * 3 * grp_coord_bytes(h->grp)));
-  HIPCHK(hipMalloc((void**)&Bt.d_abi, (size_t)k * ptb));
-  HIPCHK(hipHostMalloc((void**)&Bt.h_out, (size_t)k * ptb, hipHostMallocDefault));
-  Bt.cap = k;
-  return ZKT_OK;
-}
-// caller holds h->mu
-static int msm_batch_submit_locked(zkt_bases_impl* h, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream) {
-  if (n != h->n || k == 0 || k > ZKT_MSM_BATCH_MAX || vec_stride < n || n >= (size_t(1) << 19) || k * n > ZKT_MSM_BATCH_MAX_TERMS || (n && !dev_scalars)) return ZKT_ERR_SHAPE;
-  if (h->batch.busy) return ZKT_ERR_SHAPE;               // collect it first
-  const MsmPlan P = msm_plan_batch(n, h->grp, (int)k);
-  if (P.c != h->plan.c || P.nwin != h->plan.nwin || P.nbuckets > (size_t(1) << 21)) return ZKT_ERR_SHAPE;      // the entries index the table the handle was built with
-  int rc = batch_ready(h, (int)k); if (rc) return rc;
-  MsmBatch& Bt = h->batch;
-  hipStream_t st = batch_stream(h);
-  HIPCHK(hipEventRecord(Bt.e_in, (hipStream_t)stream));   // the scalars are produced on the caller's stream
-  HIPCHK(hipStreamWaitEvent(st, Bt.e_in, 0));
-  HIPCHK(launch_msm_sort_batch(P, h->inf, (const uint32_t*)dev_scalars, vec_stride, Bt.workspace, st));
-  HIPCHK(launch_msm_accumulate(P, h->table, Bt.workspace, st));
-  HIPCHK(launch_msm_reduce(P, Bt.workspace, Bt.d_jac, Bt.d_abi, st));
-  HIPCHK(hipMemcpyAsync(Bt.h_out, Bt.d_abi, k * abi_pt_bytes(h->grp), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipEventRecord(Bt.e_done, st));
-  Bt.k = (int)k; Bt.busy = true;
-  return ZKT_OK;
-}
-static int msm_batch_collect_locked(zkt_bases_impl* h, void* out, uint32_t* dev_partials_jac) {
-  MsmBatch& Bt = h->batch;
-  if (!Bt.busy) return ZKT_ERR_SHAPE;
-  HIPCHK(hipEventSynchronize(Bt.e_done));
-  if (dev_partials_jac) {       // copied on the batch's own stream and waited for: complete when this returns, never overtaken by the next batch
-    hipStream_t st = batch_stream(h);
-    HIPCHK(hipMemcpyAsync(dev_partials_jac, Bt.d_jac, (size_t)Bt.k * 3 * grp_coord_bytes(h->grp), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  if (out) memcpy(out, Bt.h_out, (size_t)Bt.k * abi_pt_bytes(h->grp));
-  t_kernel_ms = 0.f; t_kernel_name = "msm_batch";
-  Bt.busy = false;
-  return ZKT_OK;
-}
-static int msm_batch_submit(zkt_bases_impl* h, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!h) return ZKT_ERR_SHAPE;
-  std::lock_guard<std::mutex> lk(h->mu);
-  return msm_batch_submit_locked(h, dev_scalars, n, k, vec_stride, stream);
-}
-static int msm_batch_collect(zkt_bases_impl* h, void* out, uint32_t* dev_partials_jac) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!h) return ZKT_ERR_SHAPE;
-  std::lock_guard<std::mutex> lk(h->mu);
-  return msm_batch_collect_locked(h, out, dev_partials_jac);
-}
-static int msm_batch_dev(zkt_bases_impl* h, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream, void* out, uint32_t* dev_partials_jac) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!h || (!out && !dev_partials_jac)) return ZKT_ERR_SHAPE;
-  std::lock_guard<std::mutex> lk(h->mu);
-  int rc = msm_batch_submit_locked(h, dev_scalars, n, k, vec_stride, stream);
-  if (rc) return rc;
-  return msm_batch_collect_locked(h, out, dev_partials_jac);
-}
-// `dst` works on `src`'s streams from now on (sort stream and reduce streams [tail_base, tail_base + tail_span); the accumulate stream too if share_acc,
-// otherwise dst gets one of its own).  Call before dst's first MSM; free dst before src.
-int zkt_internal_bases_share_streams(void* dst_, void* src_, int share_acc, int tail_base, int tail_span) {
-  zkt_bases_impl *dst = (zkt_bases_impl*)dst_, *src = (zkt_bases_impl*)src_;
-  if (!dst || !src || tail_span < 1 || tail_base < 0) return ZKT_ERR_SHAPE;
-  constexpr int GROUP_TAILS = zkt_bases_impl::GROUP_TAILS;
-  if (tail_base >= GROUP_TAILS || tail_span > GROUP_TAILS) return ZKT_ERR_SHAPE;
-  int lo = 0, hi = 0; HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  {
-    std::lock_guard<std::mutex> lk(src->mu);
-    if (!src->grouped) {                       // the owner: exactly the streams the group uses (a stream that exists claims a hardware queue)
-      if (src->s_sort || src->s_acc) return ZKT_ERR_SHAPE;
-      HIPCHK(hipStreamCreateWithPriority(&src->s_sort, hipStreamNonBlocking, hi)); HIPCHK(hipStreamCreateWithPriority(&src->s_acc, hipStreamNonBlocking, lo));
-      for (int k = 0; k < GROUP_TAILS; ++k) HIPCHK(hipStreamCreateWithPriority(&src->s_tail[k], hipStreamNonBlocking, hi));
-      src->grouped = true; src->tail_base = 0; src->tail_span = 2;
-    }
-  }
-  std::lock_guard<std::mutex> lk(dst->mu);
-  if (dst->s_sort || dst->s_acc) return ZKT_ERR_SHAPE;
-  dst->own_streams = false; dst->grouped = true; dst->s_sort = src->s_sort;
-  for (int k = 0; k < GROUP_TAILS; ++k) dst->s_tail[k] = src->s_tail[k];
-  dst->tail_base = tail_base; dst->tail_span = tail_span;
-  if (share_acc) dst->s_acc = src->s_acc;
-  else { HIPCHK(hipStreamCreateWithPriority(&dst->s_acc, hipStreamNonBlocking, lo)); dst->acc_owned = true; }
-  return ZKT_OK;
-}
 // combine step of a sharded MSM: `count` Jacobian partials, `stride_words` u32 apart, summed by one wave and normalised
 int zkt_internal_jac_sum(int grp, const uint32_t* dev_partials, size_t count, size_t stride_words, hipStream_t s, void* out) {
   if (!dev_partials || !out || count == 0) return ZKT_ERR_SHAPE;
@@ -793,10 +454,11 @@ static int msm_host(int grp, const void* bases, const uint64_t* scalars, size_t 
   if (n == 0) { memset(out, 0, abi_pt_bytes(grp)); ((uint32_t*)out)[abi_pt_bytes(grp) / 4 - 2] = 1; return ZKT_OK; }
   const MsmPlan plan = msm_plan_direct(n, grp);
   const size_t ptb = abi_pt_bytes(grp), cb = grp_coord_bytes(grp);
-  uint8_t* blob = nullptr;                                   // [abi points | scalars | kernel-layout points | inf flags | jac | abi out | workspace]
   const size_t o_abi = 0, o_sc = padded(n * ptb), o_tab = o_sc + padded(n * 32), o_inf = o_tab + padded(n * 2 * cb), o_jac = o_inf + padded(n),
                o_out = o_jac + padded(4 * cb), o_ws = o_out + padded(ptb), total = o_ws + plan.ws_bytes;
-  HIPCHK(hipMalloc((void**)&blob, total));
+  Dev buf;                                                   // [abi points | scalars | kernel-layout points | inf flags | jac | abi out | workspace]
+  ZCHK(buf.alloc(total));
+  uint8_t* const blob = (uint8_t*)buf.p;
   if (debug_poison()) { HIPCHK(hipMemset(blob, 0xA5, total)); HIPCHK(hipDeviceSynchronize()); }
   std::lock_guard<std::mutex> lk(g.mu);                      // g.stream is the library's staging stream
   hipStream_t s = g.stream;
@@ -809,8 +471,7 @@ static int msm_host(int grp, const void* bases, const uint64_t* scalars, size_t 
       !fail(launch_msm_reduce(plan, blob + o_ws, (uint32_t*)(blob + o_jac), (uint32_t*)(blob + o_out), s)) &&
       !fail(hipMemcpyAsync(out, blob + o_out, ptb, hipMemcpyDeviceToHost, s)))
     fail(hipStreamSynchronize(s));
-  else hipStreamSynchronize(s);
-  hipFree(blob);
+  else (void)hipStreamSynchronize(s);                       // either way nothing is queued on the buffer when it goes
   return rc;
 }
 
@@ -936,25 +597,11 @@ int zkt_ecdsa_verify_digest_batch_dev(const uint8_t* dev_digests, const zkt_ecds
   return ZKT_OK;
 }
 
-#define ZKT_BASES_API(NAME, GRP, PT)                                                                                             \
-  int zkt_##NAME##_bases_from_device(const PT* dev, size_t n, void* stream, zkt_##NAME##_bases** out) {                          \
-    return bases_from_device(GRP, dev, n, stream, (zkt_bases_impl**)out); }                                                     \
-  int zkt_##NAME##_bases_upload(const PT* host, size_t n, zkt_##NAME##_bases** out) { return bases_upload(GRP, host, n, (zkt_bases_impl**)out); } \
-  size_t zkt_##NAME##_bases_len(const zkt_##NAME##_bases* b) { return b ? b->n : 0; }                                             \
-  void zkt_##NAME##_bases_free(zkt_##NAME##_bases* b) { bases_free(b); }                                                          \
-  int zkt_##NAME##_msm_submit(zkt_##NAME##_bases* b, const uint64_t* k, size_t n, void* stream, int slot) { return msm_submit(b, k, n, stream, slot); } \
-  int zkt_##NAME##_msm_collect(zkt_##NAME##_bases* b, int slot, PT* out, uint32_t* partial) { return msm_collect(b, slot, out, partial); } \
-  int zkt_##NAME##_msm_dev(const zkt_##NAME##_bases* b, const uint64_t* k, size_t n, void* stream, PT* out, uint32_t* partial) { \
-    return msm_dev(const_cast<zkt_##NAME##_bases*>(b), k, n, stream, out, partial); }                                              \
-  int zkt_##NAME##_msm_batch_submit(zkt_##NAME##_bases* b, const uint64_t* k, size_t n, size_t nv, size_t vs, void* stream) { return msm_batch_submit(b, k, n, nv, vs, stream); } \
-  int zkt_##NAME##_msm_batch_collect(zkt_##NAME##_bases* b, PT* out, uint32_t* partials) { return msm_batch_collect(b, out, partials); } \
-  int zkt_##NAME##_msm_batch_dev(zkt_##NAME##_bases* b, const uint64_t* k, size_t n, size_t nv, size_t vs, void* stream, PT* out, uint32_t* partials) { \
-    return msm_batch_dev(b, k, n, nv, vs, stream, out, partials); }                                                                 \
+#define ZKT_MSM_STAGED_API(NAME, GRP, PT)                                                                                        \
   int zkt_##NAME##_jac_sum_dev(const uint32_t* partials, size_t count, void* stream, PT* out) { return jac_sum_dev(GRP, partials, count, stream, out); } \
   int zkt_##NAME##_msm(const PT* bases, const uint64_t* scalars, size_t n, PT* out) { return msm_host(GRP, bases, scalars, n, out); }
-ZKT_BASES_API(g1, G_G1, zkt_g1_affine)
-ZKT_BASES_API(g2, G_G2, zkt_g2_affine)
-ZKT_BASES_API(secp, G_SECP, zkt_secp_affine)
-size_t zkt_g1_msm_workspace_bytes(size_t n) { MsmPlan p = msm_plan(n, G_G1); return p.ws_bytes + (size_t)p.nwin * n * 97; }
+ZKT_MSM_STAGED_API(g1, G_G1, zkt_g1_affine)
+ZKT_MSM_STAGED_API(g2, G_G2, zkt_g2_affine)
+ZKT_MSM_STAGED_API(secp, G_SECP, zkt_secp_affine)
 
 }  // extern "C"

@@ -381,7 +381,7 @@ int zkt_groth16_setup_r1cs_sharded(size_t n, size_t l, size_t m, const zkt_spars
   ZCHK(zkt_g1_bases_from_device((const zkt_g1_affine*)(pC.w() + (nC1 + pk->loC2) * 26), pk->hiC2 - pk->loC2, s, &pk->setC2)); pC.release();
   // one set of streams for the key (owner: setA): a sort stream, the G1 accumulate stream (C1, A, C2 in turn), B's own accumulate stream, four reduce streams —
   // with the key's own stream that is eight, one per hardware queue
-  // Sets below 2^19 terms (small circuits, and every shard of a proof spread over several GPUs) run their whole MSM on ONE stream each (zkt_api.cpp, msm_submit_locked): there
+  // Sets below 2^19 terms (small circuits, and every shard of a proof spread over several GPUs) run their whole MSM on ONE stream each (zkt_msm_handle.cpp, msm_submit): there
   // A, C1, C2 and B get a reduce stream each, so the four sums of a proof run side by side instead of one after the other (a rank's share of a 2^20-constraint proof
   // over 8 GPUs)
   const bool side_by_side = std::max(std::max(pk->hiA - pk->loA, pk->hiC1 - pk->loC1), pk->hiC2 - pk->loC2) < ((size_t)1 << 19);

@@ -1,4 +1,4 @@
-// Internal launch interface between the C ABI (zkt_api.cpp) and the HIP kernel files.
+// Internal launch interface between the C ABI (zkt_api.cpp, zkt_msm_handle.cpp) and the HIP kernel files.
 // All pointers are DEVICE pointers in the include/zkt.h layouts, viewed as u32 words.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -180,7 +180,8 @@ hipError_t zkt_launch_accumulate_g2_pair(const uint32_t* table, const uint32_t* 
 int zkt_internal_ready();                           // the library is initialised; sets the calling thread's device to the library's
 hipStream_t zkt_internal_stream();                  // the library's staging stream
 void zkt_internal_set_error_index(size_t i);        // what zkt_last_error_index reports on this thread
-// `dst` works on `src`'s streams from now on (zkt_api.cpp has the details)
+void zkt_internal_set_last_kernel(float ms, const char* name);      // what zkt_last_kernel_ms / zkt_last_kernel_name report on this thread (name: a string literal)
+// zkt_msm_handle.cpp: `dst` works on `src`'s streams from now on (the details are there)
 extern "C" int zkt_internal_bases_share_streams(void* dst, void* src, int share_acc, int tail_base, int tail_span);
 // combine step of a sharded MSM: `count` Jacobian partials, `stride_words` u32 apart, summed and normalised to one affine ABI point at host `out`
 extern "C" int zkt_internal_jac_sum(int grp, const uint32_t* dev_partials, size_t count, size_t stride_words, hipStream_t s, void* out);

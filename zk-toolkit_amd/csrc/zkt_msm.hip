@@ -757,7 +757,7 @@ MsmWs carve(const MsmPlan& P, void* workspace) {
 }
 }  // namespace
 
-// The pipeline clears its counters with a kernel of its own rather than hipMemsetAsync: inside a captured graph (zkt_api.cpp, msm_submit_locked) a memset becomes a
+// The pipeline clears its counters with a kernel of its own rather than hipMemsetAsync: inside a captured graph (zkt_msm_handle.cpp, msm_submit) a memset becomes a
 // runtime-owned node, and the pipeline's launches should be the same objects whether they are issued or replayed.
 static __global__ void __launch_bounds__(256) k_zero_words(uint32_t* __restrict__ p, int head_words, size_t quads, int tail_words) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -767,7 +767,7 @@ static __global__ void __launch_bounds__(256) k_zero_words(uint32_t* __restrict_
   if (i < (size_t)tail_words) p[(size_t)head_words + quads * 4 + i] = 0u;
 }
 // ptr 4-byte aligned (the carve puts `offsets` at 4 mod 16), bytes a multiple of 4.  Never a hipMemsetAsync: a captured graph must hold kernel nodes only
-// (zkt_api.cpp, msm_submit_locked: a runtime-owned memset node faults on the first replay after any later hipFree), and a zero-term MSM is captured like any other.
+// (zkt_msm_handle.cpp, msm_submit: a runtime-owned memset node faults on the first replay after any later hipFree), and a zero-term MSM is captured like any other.
 static hipError_t zero_async(void* ptr, size_t bytes, hipStream_t s) {
   if (bytes == 0) return hipSuccess;
   if (((uintptr_t)ptr & 3u) || (bytes & 3u)) return hipErrorInvalidValue;
