@@ -26,6 +26,8 @@ template <class C> struct PrimeOps {
   ZKT_HD static E sub2(const E& a, const E& b, const E& c) { return fp_sub2(a, b, c); }                    // a - b - 2c
   ZKT_HD static E mulsub(const E& a, const E& b, const E& c, const E& d) { return fp_mulsub(a, b, c, d); }   // a b - c d
   ZKT_HD static E neg(const E& a) { return fp_neg(a); }
+  ZKT_HD static void mul_pair(const E& a, const E& b, const E& c, const E& d, E& ab, E& cd) { fp_mul_pair(a, b, c, d, ab, cd); }
+  ZKT_HD static void sqr_pair(const E& a, const E& c, E& aa, E& cc) { fp_sqr_pair(a, c, aa, cc); }
   ZKT_HD static E inv(const E& a) { return fp_inv(a); }
   ZKT_HD static bool is_zero(const E& a) { return fp_is_zero(a); }
   ZKT_HD static bool eq(const E& a, const E& b) { return fp_eq(a, b); }
@@ -44,6 +46,8 @@ struct Fq2Ops {
   ZKT_HD static E sub2(const E& a, const E& b, const E& c) { return fq2_sub2(a, b, c); }
   ZKT_HD static E mulsub(const E& a, const E& b, const E& c, const E& d) { return fq2_mulsub(a, b, c, d); }
   ZKT_HD static E neg(const E& a) { return fq2_neg(a); }
+  ZKT_HD static void mul_pair(const E& a, const E& b, const E& c, const E& d, E& ab, E& cd) { const E r0 = fq2_mul(a, b), r1 = fq2_mul(c, d); ab = r0; cd = r1; }
+  ZKT_HD static void sqr_pair(const E& a, const E& c, E& aa, E& cc) { const E r0 = fq2_sqr(a), r1 = fq2_sqr(c); aa = r0; cc = r1; }
   ZKT_HD static E inv(const E& a) { return fq2_inv(a); }
   ZKT_HD static bool is_zero(const E& a) { return fq2_is_zero(a); }
   ZKT_HD static bool eq(const E& a, const E& b) { return fq2_eq(a, b); }
@@ -159,8 +163,31 @@ template <class F> ZKT_HD Xyzz<F> xyzz_dbl(const Xyzz<F>& p) {
   r.ZZ = F::mul(V, p.ZZ); r.ZZZ = F::mul(W, p.ZZZ);
   return r;
 }
+// madd-2008-s with the products that do not depend on each other issued as pairs (F::mul_pair / F::sqr_pair): (U2, S2), (P^2, R^2), (P PP, X1 PP),
+// (ZZ1 PP, ZZZ1 PPP); Y3 keeps the two-product scan.  The hot loop of k_accumulate<G1>: in the G1 MSM object (-DZKT_PAIR_MUL) a pair is two scans in one column
+// loop (fp.h) and xyzz_add_aff below is this function; everywhere else a pair is two calls and this is the sequence of xyzz_add_aff (csrc/hostcheck.cpp runs it).
+template <class F> ZKT_HD Xyzz<F> xyzz_add_aff_paired(const Xyzz<F>& p, const typename F::E& x2, const typename F::E& y2) {
+  typedef typename F::E E;
+  if (xyzz_is_inf(p)) return Xyzz<F>{x2, y2, F::one(), F::one()};
+  E U2, S2; F::mul_pair(x2, p.ZZ, y2, p.ZZZ, U2, S2);
+  E Pp = F::sub(U2, p.X), Rr = F::sub(S2, p.Y);
+  if (F::is_zero(Pp)) {
+    if (F::is_zero(Rr)) return xyzz_dbl_aff<F>(x2, y2);
+    return xyzz_inf<F>();
+  }
+  E PP, RR; F::sqr_pair(Pp, Rr, PP, RR);
+  E PPP, Qq; F::mul_pair(Pp, PP, p.X, PP, PPP, Qq);
+  Xyzz<F> r;
+  r.X = F::sub2(RR, PPP, Qq);
+  r.Y = F::mulsub(Rr, F::sub(Qq, r.X), p.Y, PPP);
+  F::mul_pair(p.ZZ, PP, p.ZZZ, PPP, r.ZZ, r.ZZZ);
+  return r;
+}
 // madd-2008-s: XYZZ += affine (x2, y2), 8M + 2S, complete
 template <class F> ZKT_HD Xyzz<F> xyzz_add_aff(const Xyzz<F>& p, const typename F::E& x2, const typename F::E& y2) {
+#if defined(ZKT_PAIR_MUL)
+  return xyzz_add_aff_paired<F>(p, x2, y2);
+#else
   typedef typename F::E E;
   if (xyzz_is_inf(p)) return Xyzz<F>{x2, y2, F::one(), F::one()};
   E U2 = F::mul(x2, p.ZZ), S2 = F::mul(y2, p.ZZZ);
@@ -175,6 +202,7 @@ template <class F> ZKT_HD Xyzz<F> xyzz_add_aff(const Xyzz<F>& p, const typename 
   r.Y = F::mulsub(Rr, F::sub(Qq, r.X), p.Y, PPP);
   r.ZZ = F::mul(p.ZZ, PP); r.ZZZ = F::mul(p.ZZZ, PPP);
   return r;
+#endif
 }
 // add-2008-s: XYZZ + XYZZ, 12M + 2S, complete
 template <class F> ZKT_HD Xyzz<F> xyzz_add(const Xyzz<F>& p, const Xyzz<F>& q) {

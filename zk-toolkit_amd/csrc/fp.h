@@ -361,6 +361,71 @@ template <class C> ZKT_HD void fp2_mul_kara(const Fp<C>& a0, const Fp<C>& a1, co
   }
 }
 
+// ---- paired products (W = 28): two independent Montgomery scans in ONE column loop ----------------------------------------------------------------
+// Inside one product the compiler does not keep `acc >>= 28; acc = mad64(a, b, acc)` as written: it starts every column from zero and adds the carry with a
+// 64-bit addition at the column's end (one v_lshl_add_u64 per column).  ZKT_PIN keeps a chain as written: an empty asm that owns the accumulator after every
+// multiply-add.  The compiler's hazard model assumes that a register written by inline asm may not be read by the very next instruction, so the pin of ONE chain
+// costs an s_nop per multiply-add, more than the additions it removes.  Two products that do not depend on each other lift that: their multiply-adds
+// alternate, each pin is followed by the OTHER chain's multiply-add, and neither an addition nor a wait state is left.  The scheduling barrier in ZKT_PIN keeps
+// the alternation exactly as the source has it (without it the scheduler gathers the pins and about a third of the wait states come back).
+// ZKT_PIN is empty on the host and wherever ZKT_PAIR_MUL is not defined, so the _impl functions below are ordinary code there (csrc/hostcheck.cpp runs them).
+// Column sums, bounds and results are those of fp_mul_impl / fp_sqr_impl: only the order of the additions inside a column differs.
+#if defined(ZKT_PAIR_MUL) && defined(__HIP_DEVICE_COMPILE__)
+#define ZKT_PIN(x) do { asm("" : "+v"(x)); __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define ZKT_PIN(x) ((void)0)
+#endif
+ZKT_HD uint64_t mad64p(uint32_t a, uint32_t b, uint64_t c) { uint64_t r = (uint64_t)a * b + c; ZKT_PIN(r); return r; }
+
+template <class C> ZKT_HD void fp_mul_pair_impl(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c, const Fp<C>& d, Fp<C>& ab, Fp<C>& cd) {
+  static_assert(C::W == 28, "lazy-limb fields only");
+  constexpr int N = C::N; constexpr uint32_t M = (1u << 28) - 1;
+  Fp<C> r0, r1; uint32_t m0[N], m1[N]; uint64_t s = 0, t = 0;
+#pragma unroll
+  for (int k = 0; k < 2 * N; ++k) {
+#pragma unroll
+    for (int i = (k < N ? 0 : k - N + 1); i <= (k < N ? k : N - 1); ++i) { s = mad64p(a.v[i], b.v[k - i], s); t = mad64p(c.v[i], d.v[k - i], t); }
+    if (k < N) {
+#pragma unroll
+      for (int j = 0; j < k; ++j) { s = mad64p(m0[j], C::mod(k - j), s); t = mad64p(m1[j], C::mod(k - j), t); }
+      m0[k] = ((uint32_t)s * C::INV) & M; m1[k] = ((uint32_t)t * C::INV) & M;
+      s = mad64p(m0[k], C::mod(0), s); t = mad64p(m1[k], C::mod(0), t);
+    } else {
+#pragma unroll
+      for (int j = k - N + 1; j < N; ++j) { s = mad64p(m0[j], C::mod(k - j), s); t = mad64p(m1[j], C::mod(k - j), t); }
+      r0.v[k - N] = (uint32_t)s & M; r1.v[k - N] = (uint32_t)t & M;
+    }
+    s >>= 28; t >>= 28;
+  }
+  ab = r0; cd = r1;
+}
+// the squaring scan of fp_sqr_impl, twice
+template <class C> ZKT_HD void fp_sqr_pair_impl(const Fp<C>& a, const Fp<C>& c, Fp<C>& aa, Fp<C>& cc) {
+  static_assert(C::W == 28, "lazy-limb fields only");
+  constexpr int N = C::N; constexpr uint32_t M = (1u << 28) - 1;
+  Fp<C> r0, r1; uint32_t m0[N], m1[N], d0[N], d1[N]; uint64_t s = 0, t = 0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) { d0[i] = a.v[i] << 1; d1[i] = c.v[i] << 1; }
+#pragma unroll
+  for (int k = 0; k < 2 * N; ++k) {
+#pragma unroll
+    for (int i = (k < N ? 0 : k - N + 1); 2 * i < k; ++i) { s = mad64p(d0[i], a.v[k - i], s); t = mad64p(d1[i], c.v[k - i], t); }
+    if ((k & 1) == 0) { s = mad64p(a.v[k / 2], a.v[k / 2], s); t = mad64p(c.v[k / 2], c.v[k / 2], t); }
+    if (k < N) {
+#pragma unroll
+      for (int j = 0; j < k; ++j) { s = mad64p(m0[j], C::mod(k - j), s); t = mad64p(m1[j], C::mod(k - j), t); }
+      m0[k] = ((uint32_t)s * C::INV) & M; m1[k] = ((uint32_t)t * C::INV) & M;
+      s = mad64p(m0[k], C::mod(0), s); t = mad64p(m1[k], C::mod(0), t);
+    } else {
+#pragma unroll
+      for (int j = k - N + 1; j < N; ++j) { s = mad64p(m0[j], C::mod(k - j), s); t = mad64p(m1[j], C::mod(k - j), t); }
+      r0.v[k - N] = (uint32_t)s & M; r1.v[k - N] = (uint32_t)t & M;
+    }
+    s >>= 28; t >>= 28;
+  }
+  aa = r0; cc = r1;
+}
+
 // Call policy.  One inlined multiply is ~1000 instructions (8 KB); curve and
 // pairing kernels contain hundreds of them, far beyond the 64 KB instruction
 // cache, so by default the multiply is ONE function per field and kernel image,
@@ -395,6 +460,19 @@ template <class C> ZKT_HD Fp<C> fp_muladd(const Fp<C>& a, const Fp<C>& b, const 
 // with 28-bit limbs the doubling is free (see fp_sqr_impl).
 template <class C> ZKT_HD Fp<C> fp_sqr(const Fp<C>& a) {
   if constexpr (C::W == 28) return fp_sqr_fn(a); else return fp_mul(a, a);
+}
+// (a b, c d) and (a^2, c^2): the interleaved scans in the device code of an object built with -DZKT_PAIR_MUL (W = 28), two ordinary calls everywhere else
+template <class C> ZKT_HD void fp_mul_pair(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c, const Fp<C>& d, Fp<C>& ab, Fp<C>& cd) {
+#if defined(ZKT_PAIR_MUL) && defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (C::W == 28) { fp_mul_pair_impl(a, b, c, d, ab, cd); return; }
+#endif
+  const Fp<C> r0 = fp_mul(a, b), r1 = fp_mul(c, d); ab = r0; cd = r1;
+}
+template <class C> ZKT_HD void fp_sqr_pair(const Fp<C>& a, const Fp<C>& c, Fp<C>& aa, Fp<C>& cc) {
+#if defined(ZKT_PAIR_MUL) && defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (C::W == 28) { fp_sqr_pair_impl(a, c, aa, cc); return; }
+#endif
+  const Fp<C> r0 = fp_sqr(a), r1 = fp_sqr(c); aa = r0; cc = r1;
 }
 
 // canonical words (ABI_N x 32 bit, < p) <-> internal Montgomery form

@@ -348,3 +348,7 @@ int zkt_hostcheck_ecdsa_sign(const uint8_t* digest, const uint32_t* d, const uin
   return ecdsa_sign_one(z, d, k, secp_comb_table(), sig, sig + 8) ? 1 : 0;
 }
 }  // extern "C"
+
+// ---- the paired Fq products and the paired mixed addition of the G1 accumulate loop: zkt_hostcheck_fq_pair, zkt_hostcheck_g1_acc.  Kept in a header of their
+// own so that the stand-alone sanitizer program (tests/c/acc_pairs_check.cpp) compiles them without the pairing code above.
+#include "hostcheck_acc_pairs.h"
