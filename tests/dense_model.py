@@ -16,7 +16,7 @@ CSRC = os.path.join(ROOT, "zk-toolkit_amd", "csrc")
 R = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 
 # ---- the constants the case lists were chosen for (test_dense_model compares them with the source) --------------------------------------
-LINCOMB_TPB = 256           # k_lincomb<FrC>: lanes over n (zkt_protocols.hip)
+LINCOMB_TPB = 256           # k_lincomb<FrC>: lanes over n (zkt_groth16.hip)
 POWSEQ_TPB = 256            # k_pin_powseq: lanes over max_degree (zkt_pinocchio.hip)
 EVAL_ROWS_TPB = 64          # k_eval_rows: lanes over rows (zkt_fr_vec.hip)
 PIN_SCALARS_TPB = 64        # k_pin_scalars: lanes over rows (zkt_pinocchio.hip)
@@ -54,7 +54,7 @@ def library_constants():
     d = re.findall(r"grid_blocks\(size_t n, unsigned tpb = (\d+)\)", _read("zkt_internal.h"))
     assert len(d) == 1, f"zkt_internal.h: expected one `grid_blocks(size_t n, unsigned tpb = N)`, found {d}"
     d = int(d[0])
-    proto, pin = _read("zkt_protocols.hip"), _read("zkt_pinocchio.hip")
+    proto, pin = _read("zkt_groth16.hip"), _read("zkt_pinocchio.hip")
     fast = re.findall(r"constexpr size_t PIN_FAST_IO = (\d+);", pin)
     slots = re.findall(r"PinTables tab\[(\d+)\];", pin)
     assert len(fast) == 1 and len(slots) == 1, f"zkt_pinocchio.hip: expected one `constexpr size_t PIN_FAST_IO = N;` and one `PinTables tab[N];`, found {fast} and {slots}"

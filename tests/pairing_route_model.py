@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE — python-integer model of the pairing entry points: which kernels a call takes, and what it must return.
 
 Routes.  Each pairing entry point picks a batch route by size (launch_tate, zkt_tate.hip; launch_pairing_product_check, zkt_pairing.hip;
-zkt_groth16_verify_batch, zkt_protocols.hip), then every element takes one pass: the fast loop (127 steps for a Tate value, 63 for a decision),
+zkt_groth16_verify_batch, zkt_groth16.hip), then every element takes one pass: the fast loop (127 steps for a Tate value, 63 for a decision),
 the 255-step loop (OK_REDO / TATE_MARK_LONG: Q on the twist outside G2), the reference's own chain (OK_EXACT / TATE_MARK_EXACT: P outside G1 or a point
 off its curve), a panic (an argument at infinity, or a multiple of P met by the reference's chain), or, in fail-closed mode, a rejection of what would
 have gone to the reference's chain.  `ROUTES` lists every (entry point, batch route, element pass) cell that can occur.
@@ -376,7 +376,7 @@ class Key:
         self.null_alpha_beta = null_alpha_beta
 
     def servable(self, n_stmt):
-        """ate_key_applies and ate_settle_locked (zkt_protocols.hip): the 63-step route may serve this key"""
+        """ate_key_applies and ate_settle_locked (zkt_groth16_vk_cache.cpp): the 63-step route may serve this key"""
         return (1 <= n_stmt <= 12 and not self.null_alpha_beta and self.gamma.kind == "g2" and self.delta.kind == "g2"
                 and self.kappa == self.alpha * self.beta % R)
 

@@ -1,9 +1,9 @@
-"""Bulletproofs on the GPU (zkt_protocols.hip: range proof and inner-product argument over secp256k1) compared bit for bit with the
+"""Bulletproofs on the GPU (zkt_bulletproofs.hip: range proof and inner-product argument over secp256k1) compared bit for bit with the
 discrete-log model of tests/bp_model.py at every size whose code path differs, up to 2^17.  The verdict alone cannot see every error:
 wrong but self-consistent y^i / y^-i sequences leave (65), (66-67), (68) and the argument true, and only the output points show it,
 so every case compares A, S, T1, T2, P (range proof) and L, R, P' of every level (traced argument) with the model.
 
-The sizes and the paths they reach (launch lines in zkt_protocols.hip):
+The sizes and the paths they reach (launch lines in zkt_bulletproofs.hip):
   n = 1        no IPA level: ipa_run takes the traced form even without a trace (`!out_trace && levels >= 1` fails); k_rp_fused, one block
   n = 2        one level: k_ipa_fold_tail folds it (ipa_verdict_submit), one IPA_BATCH group of one level (ipa_run collect_next)
   n = 32, 128  5 and 7 levels: the last IPA_BATCH (4) group is short (5 = 4 + 1, 7 = 4 + 3); 11 and 15 MSMs wrap the IPA_SLOTS (8) slots

@@ -104,6 +104,38 @@ def test_shutdown_then_init_rebuilds_device_bound_state():
     zk.check(L.zkt_comm_init(0, 1, None)); L.zkt_comm_finalize()
 
 
+def test_shutdown_releases_the_per_key_caches_and_init_rebuilds_them():
+    """zkt_shutdown with every per-key cache filled: the statement tables and the ate entry of a Groth16 key (zkt_groth16_vk_cache.cpp), the io tables of a
+    Pinocchio key (zkt_pinocchio.hip) and the context a one-shot range proof leaves behind (zkt_bulletproofs.hip).  After a second zkt_init the same calls
+    build them again and give the same verdicts and the same range-proof points."""
+    import pairing_route_model as M
+    from test_gpu_pairing_routes import make_key, crs_for, _proof, _fresh_alpha
+    from test_gpu_pinocchio import _instance
+    from test_oracle_protocols import range_proof_instance
+    zk.init()
+    L = zk.lib()
+    n_stmt = 3
+    key = make_key(_fresh_alpha())                                  # a key this process has not seen: its first verification is a first sight
+    crs, cbuf = crs_for(key)
+    A, B, C, stmt = _proof(key, n_stmt, 0)
+    A, B, C, W = M.g1_rows([A]), M.g2_rows([B]), M.g1_rows([C]), ints_to_arr(stmt, 4)
+    pcrs, pcbuf, pf, pbuf, io = _instance(L, 4, 511)
+    V, aL, gamma, g, h, gg, hh, rnd, u, xs = range_proof_instance(2, 2, 42)
+    def run():
+        groth = [L.zkt_groth16_verify(ctypes.byref(crs), ptr(A), ptr(B), ptr(C), ptr(W), ctypes.c_size_t(n_stmt)) for _ in range(2)]      # first sight, then from the key's ate entry
+        pin = L.zkt_pinocchio_verify(ctypes.byref(pcrs), ctypes.byref(pf), ptr(io))
+        pts = np.zeros((5, 9), np.uint64)
+        rp = L.zkt_bp_range_proof(2, ptr(V), ptr(aL), ptr(gamma), ptr(g), ptr(h), ptr(gg), ptr(hh), 1, ptr(rnd), ptr(u), ptr(xs), ptr(pts))      # host generators: the context is kept
+        return groth, pin, rp, pts
+    groth1, pin1, rp1, pts1 = run()
+    assert (groth1, pin1, rp1) == ([1, 1], 1, 1)
+    L.zkt_shutdown()
+    assert L.zkt_groth16_verify(ctypes.byref(crs), ptr(A), ptr(B), ptr(C), ptr(W), ctypes.c_size_t(n_stmt)) == -ZKT_ERR_DEVICE
+    zk.init()
+    groth2, pin2, rp2, pts2 = run()
+    assert (groth2, pin2, rp2) == (groth1, pin1, rp1) and pts1.any() and (pts2 == pts1).all()
+
+
 def test_comm_world2_callback_transport_two_processes_one_card():
     world, port = 2, 29700 + (os.getpid() % 200)
     procs = []

@@ -1,4 +1,4 @@
-// Vectors of Fr elements on the device: the helpers every Fr kernel file shares, and the host interface of zkt_fr_vec.hip (transform, prefix product, row-wise Horner).
+// Vectors of Fr elements on the device: the helpers every Fr kernel file shares (and the one block sum of the scalar-field kernels), and the host interface of zkt_fr_vec.hip (transform, prefix product, row-wise Horner).
 // An element is FW u32 words, canonical in the caller's layout or Montgomery in the library's own buffers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,6 +37,17 @@ __device__ inline Fr fr_t_at(const Fr& x, size_t n) {
   Fr one = fp_one<FrC>(), t = one, k = fp_zero<FrC>();
   for (size_t i = 1; i <= n; ++i) { k = fp_add(k, one); t = fp_mul(t, fp_sub(x, k)); }
   return t;
+}
+// Sum of one element per lane over a block of 256 lanes, any of the prime fields: an LDS tree through lds (256 * C::N words).  The sum is valid in thread 0;
+// ends on a barrier, so the caller may reuse lds at once.
+template <class C> __device__ inline Fp<C> block_sum_256(uint32_t* lds, Fp<C> acc) {
+  const int t = threadIdx.x;
+  st_raw<C>(lds + t * C::N, acc); __syncthreads();
+  for (int d = 128; d >= 1; d >>= 1) {
+    if (t < d) { acc = fp_add(acc, ld_raw<C>(lds + (t + d) * C::N)); st_raw<C>(lds + t * C::N, acc); }
+    __syncthreads();
+  }
+  return acc;
 }
 
 // ---- zkt_fr_vec.hip.  Device pointers to Montgomery elements unless said otherwise; each returns a ZKT_* status ----

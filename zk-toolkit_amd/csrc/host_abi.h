@@ -1,5 +1,5 @@
-// Host-side plumbing shared by the translation units that implement the C ABI (zkt_api.cpp, zkt_msm_handle.cpp, zkt_comm.cpp, zkt_protocols.hip,
-// zkt_pinocchio.hip, zkt_groth16_r1cs.hip): the HIP-error check, an owning device buffer, the ABI point sizes and the generators.
+// Host-side plumbing shared by the translation units that implement the C ABI (the .cpp files, and the .hip files that hold entry points of include/zkt.h):
+// the HIP-error check, an owning device buffer, the end of a verdict call, the ABI point sizes and the generators.
 // Host code only: no device header includes this file.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -40,6 +40,15 @@ struct Dev {
 // host -> the buffer's start, and device -> host, queued on s
 inline int up(Dev& d, const void* h, size_t bytes, hipStream_t s) { if (!d.p) return ZKT_ERR_DEVICE; if (bytes) HIPCHK(hipMemcpyAsync(d.p, h, bytes, hipMemcpyHostToDevice, s)); return ZKT_OK; }
 inline int down(void* h, const void* d, size_t bytes, hipStream_t s) { if (bytes) HIPCHK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s)); return ZKT_OK; }
+// The end of a call whose kernels wrote n verdicts at dok and the index of the first offending element (or NO_ERR) at derr: both come down, s is waited for,
+// and a recorded index is reported (zkt_last_error_index) with `status`.  ok == nullptr: the error word alone.  Allocates nothing.
+inline int finish_verdicts(uint32_t* ok, const void* dok, size_t n, const void* derr, hipStream_t s, int status = ZKT_ERR_INFINITY) {
+  unsigned long long e = NO_ERR; int rc;
+  if ((ok && (rc = down(ok, dok, n * 4, s))) || (rc = down(&e, derr, 8, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  if (e != NO_ERR) { zkt_internal_set_error_index((size_t)e); return status; }
+  return ZKT_OK;
+}
 
 // ABI sizes (include/zkt.h)
 constexpr size_t G1B = sizeof(zkt_g1_affine), G2B = sizeof(zkt_g2_affine), SPB = sizeof(zkt_secp_affine), FRB = 32;

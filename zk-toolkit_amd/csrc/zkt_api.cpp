@@ -194,7 +194,7 @@ void zkt_shutdown(void) {
   if (g.ready) (void)hipSetDevice(g.device);
   zkt_comm_finalize();                                // the communicator and its buffers live on this device
   zkt_poly_clear_caches();                            // twiddle tables of the polynomial entry points
-  zkt_internal_clear_caches();                        // before g.mu is taken: releasing a cached context frees base sets, which lock it themselves
+  zkt_pinocchio_clear_caches(); bp_clear_caches(); groth16_vk_clear_caches();      // before g.mu is taken: releasing a cached context frees base sets, which lock it themselves
   std::lock_guard<std::mutex> lk(g.mu);
   if (!g.ready) return;
   (void)hipSetDevice(g.device);

@@ -1,5 +1,5 @@
 // Vectors of Fr elements in HBM (fr_vec.h): the NTT of size 2^logN with its twiddle tables, the inclusive prefix product, and row-wise Horner evaluation.
-// Callers: the quotient stage and the CRS tables of zkt_groth16_r1cs.hip, the dense polynomials of zkt_poly.hip, the two dense setups (zkt_protocols.hip, zkt_pinocchio.hip).
+// Callers: the quotient stage and the CRS tables of zkt_groth16_r1cs.hip, the dense polynomials of zkt_poly.hip, the two dense setups (zkt_groth16.hip, zkt_pinocchio.hip).
 #include "fr_vec.h"
 #include "host_abi.h"
 

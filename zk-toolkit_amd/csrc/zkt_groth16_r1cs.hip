@@ -84,11 +84,7 @@ __global__ void __launch_bounds__(256) k_spmv_long(const uint32_t* __restrict__ 
   const uint32_t r = long_rows[blockIdx.x], t = threadIdx.x;
   Fr acc = fp_zero<C>();
   for (uint32_t k = ptr[r] + t; k < ptr[r + 1]; k += 256) acc = fp_add(acc, fp_mul(ldm(val + (size_t)k * FW), ldm(vec + (size_t)idx[k] * FW)));
-  stm(lds + t * FW, acc); __syncthreads();
-  for (int d = 128; d >= 1; d >>= 1) {
-    if ((int)t < d) { acc = fp_add(acc, ldm(lds + (t + d) * FW)); stm(lds + t * FW, acc); }
-    __syncthreads();
-  }
+  acc = block_sum_256<C>(lds, acc);
   if (t == 0) stm(out + (size_t)r * FW, acc);
 }
 
@@ -329,9 +325,7 @@ int zkt_groth16_setup_r1cs_sharded(size_t n, size_t l, size_t m, const zkt_spars
   hipLaunchKernelGGL(k_x_minus, dim3(grid_blocks(nx)), dim3(256), 0, s, (const uint32_t*)(consts.w() + K_X * FW), xm.w(), nx);
   ZCHK(fr_scan_mul(xm.w(), pre.w(), nx, s));
   hipLaunchKernelGGL(k_inv, dim3(grid_blocks(nx)), dim3(256), 0, s, (const uint32_t*)xm.w(), xinv.w(), nx, (unsigned long long*)derr.p);
-  unsigned long long e = NO_ERR;
-  ZCHK(down(&e, derr.p, 8, s)); HIPCHK(hipStreamSynchronize(s));
-  if (e != NO_ERR) { zkt_internal_set_error_index((size_t)e); return ZKT_ERR_INV_ZERO; }      // x fell on the domain {1..2n-1}: t(x) = 0, no CRS
+  ZCHK(finish_verdicts(nullptr, nullptr, 0, derr.p, s, ZKT_ERR_INV_ZERO));      // x fell on the domain {1..2n-1}: t(x) = 0, no CRS
   hipLaunchKernelGGL(k_setup_consts2, dim3(1), dim3(64), 0, s, (const uint32_t*)pre.w(), n, consts.w());
   hipLaunchKernelGGL(k_lagrange, dim3(grid_blocks(n)), dim3(256), 0, s, (const uint32_t*)consts.w(), (const uint32_t*)invfact.w(), (const uint32_t*)xinv.w(), n, pk->cinv.w(), Lm.w(), Lc.w());
   if (n >= 2) hipLaunchKernelGGL(k_hbasis, dim3(grid_blocks(n - 1)), dim3(256), 0, s, (const uint32_t*)consts.w(), (const uint32_t*)fact.w(), (const uint32_t*)invfact.w(), (const uint32_t*)xinv.w(), n, hbc.w(), pk->P.w());

@@ -76,7 +76,8 @@ hipError_t launch_groth16_verify(const uint32_t* A, const uint32_t* B, const uin
                                  const uint32_t* gamma, const uint32_t* delta, const uint32_t* alpha_beta, uint32_t* ok, size_t n,
                                  unsigned long long* err, hipStream_t s, const uint32_t* ate_key = nullptr);
 // what a verifying key contributes to the 63-step loop (line tables of gamma and delta, the ate counterpart of alpha_beta, verdicts on its points); layout at k_ate_key_prep
-static constexpr size_t ATE_KEY_WORDS = 2 * (size_t)68 * 84 + 144 + 1;
+static constexpr size_t ATE_KEY_TARGET = 2 * (size_t)68 * 84;      // behind the two line tables: the ate counterpart of alpha_beta (144 words), then the verdict word
+static constexpr size_t ATE_KEY_WORDS = ATE_KEY_TARGET + 144 + 1;
 hipError_t launch_ate_key_prep(const uint32_t* alpha, const uint32_t* beta, const uint32_t* gamma, const uint32_t* delta, const uint32_t* uvw_stmt, int n_stmt,
                                uint32_t* key, hipStream_t s);
 // 8-bit window tables of a key's statement points and the statement sums of a large batch from them (zkt_group.hip)
@@ -185,8 +186,9 @@ void zkt_internal_set_last_kernel(float ms, const char* name);      // what zkt_
 extern "C" int zkt_internal_bases_share_streams(void* dst, void* src, int share_acc, int tail_base, int tail_span);
 // combine step of a sharded MSM: `count` Jacobian partials, `stride_words` u32 apart, summed and normalised to one affine ABI point at host `out`
 extern "C" int zkt_internal_jac_sum(int grp, const uint32_t* dev_partials, size_t count, size_t stride_words, hipStream_t s, void* out);
-// zkt_shutdown: device memory held by the per-key caches of zkt_protocols.hip and zkt_pinocchio.hip
-extern "C" void zkt_internal_clear_caches();
+// zkt_shutdown: device memory held by the per-key caches of zkt_pinocchio.hip, zkt_bulletproofs.hip and zkt_groth16_vk_cache.cpp
 extern "C" void zkt_pinocchio_clear_caches();
+extern "C" void bp_clear_caches();
+extern "C" void groth16_vk_clear_caches();
 // zkt_shutdown: the twiddle tables of zkt_poly.hip
 extern "C" void zkt_poly_clear_caches();

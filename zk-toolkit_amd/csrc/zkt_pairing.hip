@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(64) k_stmt_sums(const uint32_t* __restrict__ t
   PtIO<FqOps>::st(out + i * ABI_G1_WORDS, jac_to_aff(acc));
 }
 // ---- the deciding entry points on the 63-step loop (pairing.h, "optimal ate") ---------------------------------------------------------
-// What a verifying key contributes, prepared ONCE per key (the host caches it by the key's bytes, zkt_protocols.hip ate_key_begin):
+// What a verifying key contributes, prepared ONCE per key (the host caches it by the key's bytes, zkt_groth16_vk_cache.cpp ate_key_begin):
 //   words [0, T)      the 68 line triples of gamma          T = ATE_LINES * ATE_LINE_WORDS
 //   words [T, 2T)     ... of delta
 //   words [2T, +144)  final_exponentiation(f_{|x|,beta}(alpha)) — the ate counterpart of the key's alpha_beta (compared in the ABI's Fq12 layout)

@@ -186,7 +186,7 @@ int pin_verify_fast(const zkt_pinocchio_crs* c, const zkt_pinocchio_proof* pf, c
   return pin_decide(e < 4 ? ZKT_ERR_INFINITY : ZKT_OK, (size_t)e, ok, e == 4 ? ZKT_ERR_INFINITY : ZKT_OK, ok[4]);
 }
 }  // namespace
-extern "C" void zkt_pinocchio_clear_caches() {      // zkt_shutdown (through zkt_internal_clear_caches)
+extern "C" void zkt_pinocchio_clear_caches() {      // zkt_shutdown
   std::lock_guard<std::mutex> lk(g_pin.mu);
   for (PinTables& t : g_pin.tab) { t.mem.reset(); t.key.clear(); t.stamp = 0; }
 }
