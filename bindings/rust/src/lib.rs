@@ -12,6 +12,7 @@
 //!   `pinocchio::*`         zk/w_trusted_setup/pinocchio/{crs,prover,verifier,proof,witness}.rs
 //!   `Signer`, `PrivateKey` building_block/curves/bls12_381/{signature,private_key}.rs
 //!   `Ecdsa`, `Signature`, `Sha256`  building_block/curves/secp256k1/ecdsa.rs, building_block/hasher/sha256.rs
+//!   `Ed25519Sha512`, `KeyPair`, `Sha512`  building_block/curves/curve25519/ed25519_sha512.rs, building_block/hasher/sha512.rs
 //! and forwards to the batch-first C ABI (`ffi`, generated from include/zkt.h).  Conventions carried over from the only native
 //! backend the reference has (building_block/mcl/): one global `init` behind `Once` that panics on failure (mcl_initializer.rs:4-15),
 //! out-parameter free functions underneath, value types with operator overloads on top.  A non-OK status becomes `panic!`, because
@@ -30,6 +31,7 @@ pub mod groth16;
 pub mod bulletproofs;
 pub mod signature;
 pub mod ecdsa;
+pub mod ed25519;
 pub mod pinocchio;
 pub mod comm;
 pub mod reference_paths;
@@ -43,6 +45,7 @@ pub use qap::QAP;
 pub use bulletproofs::Bulletproofs;
 pub use signature::{PrivateKey, Signer};
 pub use ecdsa::{Ecdsa, Sha256, Signature};
+pub use ed25519::{Ed25519Sha512, KeyPair, Sha512};
 /// the reference crate's own module paths (`building_block::curves::bls12_381::g1_point::G1Point`, `zk::w_trusted_setup::groth16::zktoolkit_based::prover::Prover`, ...)
 /// and its runtime-order `PrimeField` / `PrimeFieldElem`: reference_paths.rs
 pub use reference_paths::{building_block, zk};

@@ -163,9 +163,13 @@ pub mod building_block {
             pub mod affine_points { pub use crate::points::AffinePoints; }
             pub mod ecdsa { pub use crate::ecdsa::{Ecdsa, Signature}; }
         }
+        pub mod curve25519 {
+            pub mod ed25519_sha512 { pub use crate::ed25519::{Ed25519Sha512, KeyPair}; }
+        }
     }
     pub mod hasher {
         pub mod sha256 { pub use crate::ecdsa::Sha256; }
+        pub mod sha512 { pub use crate::ed25519::Sha512; }
     }
 }
 pub mod zk {

@@ -335,6 +335,31 @@ int zkt_ecdsa_verify_batch(const uint8_t* msgs, const uint64_t* offsets, const z
  * makes one blocking call first (zkt_ecdsa_public_keys_batch with n = 1 builds the table); every later call only launches. */
 int zkt_ecdsa_verify_digest_batch_dev(const uint8_t* dev_digests, const zkt_ecdsa_sig* dev_sigs, const zkt_secp_affine* dev_pks, size_t n, uint32_t* dev_ok, void* stream);
 
+/* SHA-512 and Ed25519 (hasher/sha512.rs, curves/curve25519/ed25519_sha512.rs, curves/curve25519/affine_point.rs): one message / one key / one signature per
+ * lane, one launch per call.  Everything is bytes, as in the reference: prv, pubs and enc are n x 32 bytes, sigs n x 64 bytes (R then S), digests n x 64 bytes.
+ * msgs / offsets follow zkt_sha256_batch exactly: n + 1 offsets, an element whose end lies before its start is an empty message, msgs may be NULL only if
+ * no offset is above 0 (the test is on the largest offset), n == 0 returns ZKT_OK, missing pointers ZKT_ERR_SHAPE.
+ * The first Ed25519 call of a process (again after zkt_shutdown) builds the comb table of B (960 entries, 92,160 bytes) and waits for it; zkt_shutdown releases it. */
+/* Hasher::get_digest of Sha512 (sha512.rs:91-97; pad_msg / compute_hash in sha_common.rs): n x 64 bytes, eight state words big-endian */
+int zkt_sha512_batch(const uint8_t* msgs, const uint64_t* offsets, size_t n, uint8_t* digests);
+/* decode_point ed25519_sha512.rs:85-98 + recover_x affine_point.rs:83-104: xy = n x 8 limbs (x[4], y[4], canonical), on_curve[i] = (x^2 == xx after the second root).
+ * Bit 255 is the parity asked of x, the rest is y taken mod q (y >= q is accepted); x is the reference's value bit for bit also where the point is off the curve. */
+int zkt_ed25519_decode_batch(const uint8_t* enc, size_t n, uint64_t* xy, uint32_t* on_curve);
+/* gen_pub_key :115-125.  The multiplier of B is s mod q as there (base_field().elem(&s), :121): it differs from the pruned s for two values no key reaches. */
+int zkt_ed25519_public_keys_batch(const uint8_t* prv, size_t n, uint8_t* pubs);
+/* sign :127-158 (deterministic: no nonce argument) */
+int zkt_ed25519_sign_batch(const uint8_t* msgs, const uint64_t* offsets, const uint8_t* prv, size_t n, uint8_t* sigs);
+/* verify :160-186, ok[i] = 1/0, never a per-element error.  As there: S >= l rejects (S read as a 256-bit integer); R is decoded and re-encoded, and the
+ * re-encoding is hashed with the key's bytes as given; B (8S mod l) == R 8 + A (8k mod l) on the full points, so a key with a torsion part verifies only where
+ * 8k mod l kills it.  The comparison is one projective accumulator [8S]B + [8k](-A) - 8R tested for the neutral element: no inversion.
+ * NOT derived from the reference's arithmetic: where R or A decodes off the curve ok[i] = 0 at once.  The reference runs its affine law on the non-point along
+ * its LSB-first chain there (false unless a 2^-250 accident occurs). */
+int zkt_ed25519_verify_batch(const uint8_t* msgs, const uint64_t* offsets, const uint8_t* sigs, const uint8_t* pubs, size_t n, uint32_t* ok);
+/* the same on device pointers (no alignment asked of them), asynchronous and ordered on `stream`.  ONE exception, as for the ECDSA form: the first Ed25519 call of
+ * a process builds the table of B on `stream` and waits for it, so it must not be made while `stream` is being captured.  A host that captures makes one blocking
+ * call first (zkt_ed25519_public_keys_batch with n = 1); every later call only launches. */
+int zkt_ed25519_verify_batch_dev(const uint8_t* dev_msgs, const uint64_t* dev_offsets, const uint8_t* dev_sigs, const uint8_t* dev_pubs, size_t n, uint32_t* dev_ok, void* stream);
+
 /* f-4: Pinocchio (protocol 2 of eprint 2013/279) — CRS (EvaluationKeys crs.rs:12-22, VerificationKeys crs.rs:24-39), CRS::new crs.rs:49-161,
  * Prover::prove pinocchio/prover.rs:98-170, Verifier::verify pinocchio/verifier.rs:31-85, Proof proof.rs:6-17.  vi/wi/yi are the
  * (n_io + n_mid) x n dense Fr coefficient arrays of Prover.vi/wi/yi (prover.rs:43-45), low degree first; wires 0..n_io-1 are

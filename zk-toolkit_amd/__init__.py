@@ -116,6 +116,13 @@ def lib():
         L.zkt_ecdsa_verify_digest_batch.argtypes = [vp, vp, vp, sz, vp]
         L.zkt_ecdsa_verify_batch.argtypes = [vp, vp, vp, vp, sz, vp]
         L.zkt_ecdsa_verify_digest_batch_dev.argtypes = [vp, vp, vp, sz, vp, vp]
+        # SHA-512 and Ed25519: bytes throughout
+        L.zkt_sha512_batch.argtypes = [vp, vp, sz, vp]
+        L.zkt_ed25519_decode_batch.argtypes = [vp, sz, vp, vp]
+        L.zkt_ed25519_public_keys_batch.argtypes = [vp, sz, vp]
+        L.zkt_ed25519_sign_batch.argtypes = [vp, vp, vp, sz, vp]
+        L.zkt_ed25519_verify_batch.argtypes = [vp, vp, vp, vp, sz, vp]
+        L.zkt_ed25519_verify_batch_dev.argtypes = [vp, vp, vp, vp, sz, vp, vp]
         _lib = L
     return _lib
 

@@ -352,3 +352,74 @@ int zkt_hostcheck_ecdsa_sign(const uint8_t* digest, const uint32_t* d, const uin
 // ---- the paired Fq products and the paired mixed addition of the G1 accumulate loop: zkt_hostcheck_fq_pair, zkt_hostcheck_g1_acc.  Kept in a header of their
 // own so that the stand-alone sanitizer program (tests/c/acc_pairs_check.cpp) compiles them without the pairing code above.
 #include "hostcheck_acc_pairs.h"
+
+// ---- SHA-512 and Ed25519 (sha512.h, fe25519.h, ed25519.h): the per-message, per-key and per-signature functions the kernels of zkt_ed25519.hip run, on the host ----
+#include "ed25519.h"
+namespace {
+// the base point's comb table as k_ed25519_table writes it: [w * 15 + d - 1] = d * 16^w * B as (y-x, y+x, 2dxy)
+const uint32_t* ed25519_comb_table() {
+  static std::vector<uint32_t> t;
+  if (!t.empty()) return t.data();
+  t.resize((size_t)ED_COMB_ENTRIES * ED_PRE_WORDS);
+  for (int e = 0; e < ED_COMB_ENTRIES; ++e) ed25519_comb_entry(e, t.data() + (size_t)e * ED_PRE_WORDS);
+  return t.data();
+}
+}  // namespace
+extern "C" {
+// digest (64 bytes) of prefix[0..plen) ‖ msg[0..len), plen in {0, 32, 64}: the prefix goes in as register words, as the kernels pass it; msg may have any alignment
+int zkt_hostcheck_sha512(const uint8_t* prefix, size_t plen, const uint8_t* msg, size_t len, uint8_t* digest) {
+  uint64_t pre[8] = {0, 0, 0, 0, 0, 0, 0, 0}, h[8];
+  if (plen != 0 && plen != 32 && plen != 64) return -1;
+  for (size_t i = 0; i < plen; ++i) pre[i / 8] |= (uint64_t)prefix[i] << (56 - 8 * (i % 8));
+  if (plen == 0) sha512_words<0>(pre, msg, len, h); else if (plen == 32) sha512_words<4>(pre, msg, len, h); else sha512_words<8>(pre, msg, len, h);
+  sha512_store_digest(h, digest);
+  return 0;
+}
+// one compression: h (8 words) updated by the block w (16 big-endian words)
+int zkt_hostcheck_sha512_compress(uint64_t* h, const uint64_t* w) { uint64_t blk[16]; for (int i = 0; i < 16; ++i) blk[i] = w[i]; sha512_compress(h, blk); return 0; }
+// byte `pos` of the padded message of a len-byte msg (pad_msg), and the padded length through *padded_len
+int zkt_hostcheck_sha512_pad(const uint8_t* msg, size_t len, size_t pos, size_t* padded_len) {
+  const uint64_t pl = sha512_padded_len(len); if (padded_len) *padded_len = (size_t)pl;
+  return pos < pl ? (int)sha512_padded_byte(msg, 0, len, pl, pos) : -1;
+}
+// field mod 2^255 - 19: a, b are ANY 8-word values (not reduced), o is the canonical result
+int zkt_hostcheck_fe25519_mul(const uint32_t* a, const uint32_t* b, uint32_t* o) { fe_to_words(fe_mul(fe_from_words(a), fe_from_words(b)), o); return 0; }
+int zkt_hostcheck_fe25519_sqr(const uint32_t* a, uint32_t* o) { fe_to_words(fe_sqr(fe_from_words(a)), o); return 0; }
+int zkt_hostcheck_fe25519_inv(const uint32_t* a, uint32_t* o) { fe_to_words(fe_inv(fe_from_words(a)), o); return 0; }
+// op 0 add, 1 sub, 2 neg (b unused)
+int zkt_hostcheck_fe25519_lin(int op, const uint32_t* a, const uint32_t* b, uint32_t* o) {
+  const Fe x = fe_from_words(a), y = fe_from_words(b);
+  fe_to_words(op == 0 ? fe_add(x, y) : op == 1 ? fe_sub(x, y) : fe_neg(x), o); return 0;
+}
+// fe_sqrt_ratio: x = (u/v)^((q+3)/8), times I if its square is not u/v; returns whether the square of the x handed back is u/v (v != 0)
+int zkt_hostcheck_fe25519_sqrt_ratio(const uint32_t* u, const uint32_t* v, uint32_t* x) {
+  Fe r; const bool ok = fe_sqrt_ratio(fe_from_words(u), fe_from_words(v), r); fe_to_words(r, x); return ok ? 1 : 0;
+}
+// integers mod l: x (16 words) mod l; (a b + c) mod l
+int zkt_hostcheck_sc25519_reduce512(const uint32_t* x, uint32_t* r) { sc_reduce512(x, r); return 0; }
+int zkt_hostcheck_sc25519_muladd(const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* r) { sc_muladd(a, b, c, r); return 0; }
+// ed25519_decode_one: enc 32 bytes -> xy = x (8 words), y (8 words), canonical; returns the on-curve flag
+int zkt_hostcheck_ed25519_decode(const uint8_t* enc, uint32_t* xy) {
+  uint32_t w[8]; Fe x, y;
+  ld_le_words(enc, w, 8);
+  const bool on = ed25519_decode_one(w, x, y);
+  fe_to_words(x, xy); fe_to_words(y, xy + 8);
+  return on ? 1 : 0;
+}
+// ed25519_pub_from_scalar: the already pruned 32-byte scalar s (so that s >= q can be given) -> enc(B (s mod q))
+int zkt_hostcheck_ed25519_pub_from_scalar(const uint8_t* s, uint8_t* pub) {
+  uint32_t w[8], enc[8];
+  ld_le_words(s, w, 8);
+  ed25519_pub_from_scalar(w, ed25519_comb_table(), enc);
+  st_le_words(pub, enc, 8);
+  return 0;
+}
+int zkt_hostcheck_ed25519_public_key(const uint8_t* prv, uint8_t* pub) { ed25519_public_key_one(prv, ed25519_comb_table(), pub); return 0; }
+int zkt_hostcheck_ed25519_sign(const uint8_t* msg, size_t len, const uint8_t* prv, uint8_t* sig) { ed25519_sign_one(msg, len, prv, ed25519_comb_table(), sig); return 0; }
+// ed25519_verify_one with the window table in the caller's frame (stride 1) or word-interleaved as the LDS form lays it out (stride 64)
+int zkt_hostcheck_ed25519_verify(const uint8_t* msg, size_t len, const uint8_t* sig, const uint8_t* pub, int stride) {
+  if (stride == 64) { std::vector<uint32_t> tab((size_t)ED_TAB * ED_CW * 64); return ed25519_verify_one<64>(msg, len, sig, pub, ed25519_comb_table(), tab.data() + 5) ? 1 : 0; }
+  uint32_t tab[ED_TAB * ED_CW];
+  return ed25519_verify_one<1>(msg, len, sig, pub, ed25519_comb_table(), tab) ? 1 : 0;
+}
+}  // extern "C"

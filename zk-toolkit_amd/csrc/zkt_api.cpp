@@ -199,6 +199,7 @@ void zkt_shutdown(void) {
   if (!g.ready) return;
   (void)hipSetDevice(g.device);
   group_release_device_state();                       // generator comb tables
+  ed25519_release_device_state();                     // the comb table of the Ed25519 base point
   pairing_release_device_state();                     // guard side stream + events
   tate_events_release();
   if (g.arena) (void)hipFree(g.arena);
@@ -597,7 +598,98 @@ int zkt_ecdsa_verify_digest_batch_dev(const uint8_t* dev_digests, const zkt_ecds
   return ZKT_OK;
 }
 
-#define ZKT_MSM_STAGED_API(NAME, GRP, PT)                                                                                        \
+// ---- SHA-512 and Ed25519 (zkt_ed25519.hip): bytes in, bytes out, staged like the ECDSA calls --------------------------------------------------------
+namespace {
+// messages (optional) + offsets, then `a` and `b` (n x a_bytes, n x b_bytes: signatures and keys), then n x out_bytes of output.  Caller holds g.mu.
+struct EdStage { uint8_t *msgs = nullptr, *a = nullptr, *b = nullptr, *out = nullptr; unsigned long long* off = nullptr; };
+int ed_stage(const uint8_t* msgs, const uint64_t* offsets, const void* a, size_t a_bytes, const void* b, size_t b_bytes, size_t out_bytes, size_t n, EdStage& st) {
+  const size_t total = offsets ? msgs_extent(offsets, n) : 0;
+  if (total && !msgs) return ZKT_ERR_SHAPE;                      // the extent, not offsets[n]
+  ZCHK(arena_reserve(padded(total) + padded((n + 1) * 8) + padded(n * a_bytes) + padded(n * b_bytes) + padded(n * out_bytes) + 2048));
+  Carver cv(g.arena);
+  if (offsets) {
+    st.msgs = cv.take<uint8_t>(total); st.off = cv.take<unsigned long long>((n + 1) * 8);
+    if (total) HIPCHK(hipMemcpyAsync(st.msgs, msgs, total, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(st.off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, g.stream));
+  }
+  st.a = cv.take<uint8_t>(n * a_bytes); st.b = cv.take<uint8_t>(n * b_bytes); st.out = cv.take<uint8_t>(n * out_bytes);
+  if (a_bytes) HIPCHK(hipMemcpyAsync(st.a, a, n * a_bytes, hipMemcpyHostToDevice, g.stream));
+  if (b_bytes) HIPCHK(hipMemcpyAsync(st.b, b, n * b_bytes, hipMemcpyHostToDevice, g.stream));
+  return ZKT_OK;
+}
+int ed_finish(void* out, const EdStage& st, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(out, st.out, bytes, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  return ZKT_OK;
+}
+}  // namespace
+int zkt_sha512_batch(const uint8_t* msgs, const uint64_t* offsets, size_t n, uint8_t* digests) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!offsets || !digests) return ZKT_ERR_SHAPE;
+  if (n == 0) return ZKT_OK;
+  std::lock_guard<std::mutex> lk(g.mu);
+  EdStage st;
+  ZCHK(ed_stage(msgs, offsets, nullptr, 0, nullptr, 0, 64, n, st));
+  HIPCHK(launch_sha512(st.msgs, st.off, n, st.out, g.stream));
+  return ed_finish(digests, st, n * 64);
+}
+int zkt_ed25519_decode_batch(const uint8_t* enc, size_t n, uint64_t* xy, uint32_t* on_curve) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!enc || !xy || !on_curve) return ZKT_ERR_SHAPE;
+  if (n == 0) return ZKT_OK;
+  std::lock_guard<std::mutex> lk(g.mu);
+  EdStage st;
+  ZCHK(ed_stage(nullptr, nullptr, enc, 32, nullptr, 0, 64 + 4, n, st));
+  uint32_t* dxy = (uint32_t*)st.out; uint32_t* dflag = dxy + n * 16;
+  HIPCHK(launch_ed25519_decode(st.a, n, dxy, dflag, g.stream));
+  HIPCHK(hipMemcpyAsync(on_curve, dflag, n * 4, hipMemcpyDeviceToHost, g.stream));
+  return ed_finish(xy, st, n * 64);
+}
+int zkt_ed25519_public_keys_batch(const uint8_t* prv, size_t n, uint8_t* pub) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!prv || !pub) return ZKT_ERR_SHAPE;
+  if (n == 0) return ZKT_OK;
+  std::lock_guard<std::mutex> lk(g.mu);
+  EdStage st; const uint32_t* btab = nullptr;
+  HIPCHK(ed25519_base_table(&btab, g.stream));
+  ZCHK(ed_stage(nullptr, nullptr, prv, 32, nullptr, 0, 32, n, st));
+  HIPCHK(launch_ed25519_public_keys(st.a, btab, n, st.out, g.stream));
+  return ed_finish(pub, st, n * 32);
+}
+int zkt_ed25519_sign_batch(const uint8_t* msgs, const uint64_t* offsets, const uint8_t* prv, size_t n, uint8_t* sigs) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!offsets || !prv || !sigs) return ZKT_ERR_SHAPE;
+  if (n == 0) return ZKT_OK;
+  std::lock_guard<std::mutex> lk(g.mu);
+  EdStage st; const uint32_t* btab = nullptr;
+  HIPCHK(ed25519_base_table(&btab, g.stream));
+  ZCHK(ed_stage(msgs, offsets, prv, 32, nullptr, 0, 64, n, st));
+  HIPCHK(launch_ed25519_sign(st.msgs, st.off, st.a, btab, n, st.out, g.stream));
+  return ed_finish(sigs, st, n * 64);
+}
+int zkt_ed25519_verify_batch(const uint8_t* msgs, const uint64_t* offsets, const uint8_t* sigs, const uint8_t* pub, size_t n, uint32_t* ok) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!offsets || !sigs || !pub || !ok) return ZKT_ERR_SHAPE;
+  if (n == 0) return ZKT_OK;
+  std::lock_guard<std::mutex> lk(g.mu);
+  EdStage st; const uint32_t* btab = nullptr;
+  HIPCHK(ed25519_base_table(&btab, g.stream));
+  ZCHK(ed_stage(msgs, offsets, sigs, 64, pub, 32, 4, n, st));
+  HIPCHK(launch_ed25519_verify(st.msgs, st.off, st.a, st.b, btab, n, (uint32_t*)st.out, g.stream));
+  return ed_finish(ok, st, n * 4);
+}
+// device pointers, ordered on the caller's stream: nothing is staged and nothing waits (but for the first call of a process, which builds the table of B on that stream)
+int zkt_ed25519_verify_batch_dev(const uint8_t* dev_msgs, const uint64_t* dev_offsets, const uint8_t* dev_sigs, const uint8_t* dev_pub, size_t n, uint32_t* dev_ok, void* stream) {
+  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
+  if (!dev_offsets || !dev_sigs || !dev_pub || !dev_ok) return ZKT_ERR_SHAPE;      // dev_msgs may be NULL when every message is empty: the offsets are on the device, not looked at here
+  if (n == 0) return ZKT_OK;
+  const uint32_t* btab = nullptr;
+  HIPCHK(ed25519_base_table(&btab, (hipStream_t)stream));
+  HIPCHK(launch_ed25519_verify(dev_msgs, (const unsigned long long*)dev_offsets, dev_sigs, dev_pub, btab, n, dev_ok, (hipStream_t)stream));
+  return ZKT_OK;
+}
+
+#define ZKT_MSM_STAGED_API(NAME, GRP, PT)                                                                                       \
   int zkt_##NAME##_jac_sum_dev(const uint32_t* partials, size_t count, void* stream, PT* out) { return jac_sum_dev(GRP, partials, count, stream, out); } \
   int zkt_##NAME##_msm(const PT* bases, const uint64_t* scalars, size_t n, PT* out) { return msm_host(GRP, bases, scalars, n, out); }
 ZKT_MSM_STAGED_API(g1, G_G1, zkt_g1_affine)

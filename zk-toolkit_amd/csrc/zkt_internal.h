@@ -134,6 +134,19 @@ hipError_t launch_ecdsa_verify(const uint8_t* digests, const uint8_t* msgs, cons
 hipError_t launch_ecdsa_sign(const uint8_t* digests, const uint8_t* msgs, const unsigned long long* off, const uint32_t* sks, const uint32_t* ks,
                              const uint32_t* gtab, uint32_t* sigs, uint32_t* retry, size_t n, hipStream_t s);
 
+// ---- SHA-512 and Ed25519 (zkt_ed25519.hip): bytes throughout, one lane per element ------------------------------------------------
+// digests[i] = SHA-512(msgs[off[i] .. off[i+1])), 64 bytes each
+hipError_t launch_sha512(const uint8_t* msgs, const unsigned long long* off, size_t n, uint8_t* digests, hipStream_t s);
+// the comb table of B, built on first use on `s` (which is then waited for): 960 entries [w * 15 + d - 1] = d * 16^w * B as (y-x, y+x, 2dxy)
+hipError_t ed25519_base_table(const uint32_t** table, hipStream_t s);
+void ed25519_release_device_state();                 // zkt_shutdown
+// enc: n x 32 bytes -> xy: n x 16 words (x, y canonical), on_curve: n flags
+hipError_t launch_ed25519_decode(const uint8_t* enc, size_t n, uint32_t* xy, uint32_t* on_curve, hipStream_t s);
+hipError_t launch_ed25519_public_keys(const uint8_t* prv, const uint32_t* btab, size_t n, uint8_t* pub, hipStream_t s);
+hipError_t launch_ed25519_sign(const uint8_t* msgs, const unsigned long long* off, const uint8_t* prv, const uint32_t* btab, size_t n, uint8_t* sigs, hipStream_t s);
+hipError_t launch_ed25519_verify(const uint8_t* msgs, const unsigned long long* off, const uint8_t* sigs, const uint8_t* pub, const uint32_t* btab, size_t n, uint32_t* ok,
+                                 hipStream_t s);
+
 // ---- MSM (zkt_msm.hip), generic over the group (G_G1, G_G2, G_SECP) ------------------------------------------
 struct MsmPlan {
   size_t n;            // terms
