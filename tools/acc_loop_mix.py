@@ -2,10 +2,12 @@
 """Instruction mix of the bucket-accumulation hot loop, from the compiler's assembly.  No GPU needed.
 
 Compiles csrc/zkt_msm.hip to gfx950 assembly with exactly the flags of the Makefile's zkt_msm.o rule (the G1 object; the command line is
-taken from `make -n`, so the two cannot drift apart), finds k_accumulate<FqOps> (G1), and prints for every basic block above --min-block
+taken from `make -n`, so the two cannot drift apart), finds k_accumulate of the G1 field, and prints for every basic block above --min-block
 instructions its size, its VALU mix (ordinary v_* mnemonics) and its s_nop count, then the kernel's register, scratch and occupancy
 figures from the code object's metadata.  The steady-state iteration of the accumulate loop is the sum of those blocks without the doubling exits, which are
 told by their multiply-add count (about 2,333 in one block; the mixed addition's 8 products, 2 squarings and 9 reductions are about 3,550 over its blocks); its totals are printed last.
+With the object on 13 x 30-bit limbs (the Makefile's FQ30FLAGS, part of the command line taken from `make -n`) the kernel is k_accumulate<PrimeOps<Fq30C>>, a doubling exit
+holds about 2,021 multiply-adds and the mixed addition about 3,090.  `make -n` is run with this process's environment, so FQ30FLAGS= in the environment gives the 14 x 28 object.
 
 usage: tools/acc_loop_mix.py [--min-block 300] [--kernel k_accumulate] [--keep out.s | --asm in.s] [extra compiler flags ...]
 """
@@ -30,7 +32,7 @@ def compile_to_asm(out_s, extra):
 
 def kernel_body(text, want):
     """(mangled name, lines) of the one kernel whose name holds `want`, instantiated for Fq"""
-    m = [n for n in re.findall(r"^(_Z\w+):", text, re.M) if want in n and "3FqC" in n]
+    m = [n for n in re.findall(r"^(_Z\w+):", text, re.M) if want in n and ("3FqC" in n or "5Fq30C" in n)]      # the G1 object's field: 14 x 28 or 13 x 30 limbs
     assert len(m) == 1, m
     name = m[0]
     body = text[text.index("\n" + name + ":"):text.index(".Lfunc_end", text.index("\n" + name + ":"))]
@@ -75,6 +77,7 @@ def main():
             text = open(out_s).read()
     name, lines = kernel_body(text, args.kernel)
     loop = collections.Counter()
+    dbl_exit = 2021 if "5Fq30C" in name else 2333      # multiply-adds of a doubling-exit block: 13 x 30 limbs (338 per product), 14 x 28 (392)
     print("# " + re.sub(r"\S*/(?=zkt_msm\.s)", "", cmd.replace(ROOT + "/", "")))
     print("kernel %s" % name)
     for label, ins in blocks(lines).items():
@@ -83,7 +86,7 @@ def main():
         print("block %s: %d instructions, %d VALU, %d s_nop, %d s_waitcnt" % (label, len(ins), sum(mix.values()), sum(1 for i in ins if i == "s_nop"), sum(1 for i in ins if i == "s_waitcnt")))
         print("   " + "  ".join("%s %d" % (k.replace("_e32", "").replace("_e64", ""), v) for k, v in mix.most_common() if v >= 8) + "  (others %d)" % sum(v for v in mix.values() if v < 8))
         # the mixed addition: every big block but the doubling exits, which hold two squarings more and two products fewer and so about 2,333 multiply-adds
-        if abs(mix["v_mad_u64_u32"] - 2333) > 20:
+        if abs(mix["v_mad_u64_u32"] - dbl_exit) > 20:
             loop.update(ins); loop["blocks"] += 1
     print("steady-state iteration (the %d blocks above that are not doubling exits): %d instructions, %d v_mad_u64_u32, %d v_lshl_add_u64, %d s_nop" %
           (loop.pop("blocks", 0), sum(loop.values()), loop["v_mad_u64_u32"], loop["v_lshl_add_u64"], loop["s_nop"]))

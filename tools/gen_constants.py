@@ -35,7 +35,9 @@ def arr_w(v):
 
 def field(name, p, n, doc, w=32):
     """w = 32: n x 32-bit limbs, canonical Montgomery residues, carry-chain add/sub (Fr, secp256k1 fields).
-       w = 28: n x 28-bit limbs, lazy residues < 4p, R = 2^(28n): the multiply needs no carry chain (Fq, the hot field)."""
+       w = 28: n x 28-bit limbs, lazy residues < 4p, R = 2^(28n): the multiply needs no carry chain (Fq, the hot field).
+       w = 30: the same lazy form on n x 30-bit limbs (Fq in the G1 MSM object: 13 limbs instead of 14).  A full column of a product scan no longer
+               fits 64 bits; split_masks() below derives, from exact worst-case bounds, where a column's running sum must hand its carry over."""
     Rm = (1 << (w * n)) % p
     inv = (-pow(p, -1, 1 << w)) % (1 << w)
     abi_n = (p.bit_length() + 31) // 32
@@ -53,7 +55,7 @@ def field(name, p, n, doc, w=32):
         s.append(f"  ZKT_HD static constexpr uint32_t {fn}(int i) {{ constexpr uint32_t t[{n}] = {arr_w(val)}; return t[i]; }}")
     s.append(f"  ZKT_HD static constexpr uint32_t mod32(int i) {{ constexpr uint32_t t[{abi_n}] = {arr_w(limbs_w(p, abi_n, 32))}; return t[i]; }}")
     s.append(f"  ZKT_HD static constexpr uint32_t pm2(int i) {{ constexpr uint32_t t[{abi_n}] = {arr_w(limbs_w(p - 2, abi_n, 32))}; return t[i]; }}   // p-2, 32-bit words")
-    if w == 28:
+    if w in (28, 30):
         k8 = limbs_w(8 * p, n, w)
         subk = [k8[0] + (1 << w)] + [k8[i] + (1 << w) - 1 for i in range(1, n - 1)] + [k8[n - 1] - 1]
         assert sum(v << (w * i) for i, v in enumerate(subk)) == 8 * p and all(v >= (1 << w) - 1 for v in subk[:-1])
@@ -61,16 +63,73 @@ def field(name, p, n, doc, w=32):
         top = p >> (w * (n - 1))
         s.append(f"  ZKT_HD static constexpr uint32_t subk(int i) {{ constexpr uint32_t t[{n}] = {arr_w(subk)}; return t[i]; }}   // 8p with borrow-safe limbs")
         k16 = limbs_w(16 * p, n, w)
-        subk3 = [k16[0] + 4 * (1 << w)] + [k16[i] + 4 * (1 << w) - 4 for i in range(1, n - 1)] + [k16[n - 1] - 4]
+        # every limb must cover b + 2c <= 3 (2^w - 1): lend 4 units of the next limb where a u32 has the room (w = 28), 3 where it has not (w = 30)
+        lend = 4 if w == 28 else 3
+        subk3 = [k16[0] + lend * (1 << w)] + [k16[i] + lend * (1 << w) - lend for i in range(1, n - 1)] + [k16[n - 1] - lend]
         assert sum(v << (w * i) for i, v in enumerate(subk3)) == 16 * p and all(v >= 3 * ((1 << w) - 1) for v in subk3[:-1])
-        assert subk3[-1] >= 3 * ((4 * p) >> (w * (n - 1))) + 3 and max(subk3) + (1 << w) < (1 << 31)
+        assert subk3[-1] >= 3 * ((4 * p) >> (w * (n - 1))) + 3
+        if w == 28:
+            assert max(subk3) + (1 << w) < (1 << 31)
+        else:
+            # w = 30: a + subk - b (+ the reduction's carry < 2^6) fits a u32; subk3 - b - 2c fits a u32 on its own and meets a in the 64-bit sum of fp_lazy_reduce2
+            assert max(subk) + (1 << w) + 64 < (1 << 32) and max(subk3) < (1 << 32)
         s.append(f"  ZKT_HD static constexpr uint32_t subk3(int i) {{ constexpr uint32_t t[{n}] = {arr_w(subk3)}; return t[i]; }}   // 16p, every limb covers b + 2c for b, c < 4p")
         s.append(f"  ZKT_HD static constexpr uint32_t comp(int i) {{ constexpr uint32_t t[{n}] = {arr_w(limbs_w((1 << (w * n)) - p, n, w))}; return t[i]; }}   // 2^(WN) - p")
         s.append(f"  static constexpr uint32_t QEST_M = {(1 << 32) // (top + 1)}u;   // floor(2^32 / (floor(p / 2^(W(N-1))) + 1))")
         body = "{" + ",".join(arr_w(limbs_w(j * p, n, w)) for j in range(4)) + "}"
         s.append(f"  ZKT_HD static constexpr uint32_t kp(int j, int i) {{ constexpr uint32_t t[4][{n}] = {body}; return t[j][i]; }}   // j*p, j<4")
+    if w == 30:
+        masks, carry = split_masks(limbs_w(p, n, w), subk, n, w)
+        for kind in ("mul", "sqr", "mul2"):
+            vals = "{" + ",".join("0x%xull" % v for v in masks[kind]) + "}"
+            cols = [k for k, v in enumerate(masks[kind]) if v]
+            s.append(f"  // columns {cols}; the carry out of a column stays below 2^{max(carry[kind]).bit_length()}")
+            s.append(f"  ZKT_HD static constexpr uint64_t split_{kind}(int k) {{ constexpr uint64_t t[{2 * n}] = {vals}; return t[k]; }}")
     s.append("};")
     return "\n".join(s)
+
+
+def scan_terms(kind, k, pl, subk, n, w):
+    """Worst-case value of every multiply-add of column k of a product scan, in the order fp.h issues them (limbs < 2^w on both sides unless said otherwise):
+       mul   a_i b_(k-i), then m_j p_(k-j) with the exact limbs of p
+       sqr   (2 a_i) a_(k-i) for 2i < k, a_(k/2)^2, then the reduction
+       mul2  a_i b_(k-i) and c_i (8p spread - d)_(k-i) alternating, then the reduction"""
+    M = (1 << w) - 1
+    lo, hi = (0, k) if k < n else (k - n + 1, n - 1)
+    t = []
+    if kind == "mul":
+        t += [M * M for i in range(lo, hi + 1)]
+    elif kind == "sqr":
+        t += [2 * M * M for i in range(lo, hi + 1) if 2 * i < k] + ([M * M] if k % 2 == 0 else [])
+    else:
+        for i in range(lo, hi + 1):
+            t += [M * M, M * subk[k - i]]
+    if k < n:
+        t += [M * pl[k - j] for j in range(k)] + [M * pl[0]]
+    else:
+        t += [M * pl[k - j] for j in range(k - n + 1, n)]
+    return t
+
+
+def split_masks(pl, subk, n, w):
+    """Where a column of a 30-bit-limb product scan hands its carry over.  The 64-bit accumulator enters a column with the carry of the one before; bit t of a column's
+    mask says: before multiply-add t, move the accumulator's bits above 2^w to a second register and go on from the low w bits.  A split is placed exactly where the
+    worst case of the running sum (every operand limb 2^w - 1, the limbs of p and of the 8p spread exact) would reach 2^64, so columns that cannot overflow have mask 0."""
+    M = (1 << w) - 1
+    masks, carries = {}, {}
+    for kind in ("mul", "sqr", "mul2"):
+        ms, cs, carry = [], [], 0
+        for k in range(2 * n):
+            run, hi, mask = carry, 0, 0
+            for t, v in enumerate(scan_terms(kind, k, pl, subk, n, w)):
+                if run + v >= 1 << 64:
+                    mask |= 1 << t; hi += run >> w; run = min(run, M)
+                    assert run + v < 1 << 64
+                run += v
+            carry = (run >> w) + hi
+            ms.append(mask); cs.append(carry)
+        masks[kind], carries[kind] = ms, cs
+    return masks, carries
 
 
 def mont(x, p, n):
@@ -84,6 +143,7 @@ out.append("#include <stdint.h>")
 out.append("#ifndef ZKT_HD\n#define ZKT_HD __host__ __device__ __forceinline__\n#endif\n// real functions (bounded code size / compile time): big field and tower operations\n#ifndef ZKT_FN\n#define ZKT_FN __host__ __device__ inline __attribute__((noinline))\n#endif")
 out.append("namespace zkt {")
 out.append(field("FqC", Q, 14, "BLS12-381 base field q (params.rs:9): 14 x 28-bit lazy limbs", w=28))
+out.append(field("Fq30C", Q, 13, "BLS12-381 base field q on 13 x 30-bit lazy limbs, R = 2^390: the G1 MSM object (fp.h, W = 30)", w=30))
 out.append(field("FrC", R, 8, "BLS12-381 subgroup order r (params.rs:14)"))
 out.append(field("SpC", SP, 8, "secp256k1 base field p (secp256k1/affine_point.rs:30-47)"))
 out.append(field("SnC", SN, 8, "secp256k1 group order n"))

@@ -7,6 +7,11 @@
 //           multiply is pure v_mad_u64_u32 (no v_addc per product), squaring can share
 //           cross products, and add/sub are carry-free limb adds plus one fused
 //           "subtract floor-estimate * p and propagate" pass (fp_lazy_reduce).
+//   W = 30  N x 30-bit limbs, R = 2^(30N), the same lazy form (< 4p, limbs < 2^30): Fq30C, BLS12-381 Fq on 13 limbs instead of 14 in the G1 MSM object
+//           (338 instead of 392 multiply-adds per product).  13 products < 2^60 and 13 reduction products do not always fit one 64-bit column: in the columns
+//           tools/gen_constants.py lists (C::split_*: 10..14 of a product) the accumulator hands its bits above 2^30 to a second register in mid-column
+//           (fp_split below).  Sums and differences: the bounds are stated at each form; fp_sub2 needs the 64-bit pass fp_lazy_reduce2.
+//   "lazy" below means W < 32; the W = 28 code is what it was before W = 30 existed (the split masks of a W = 28 field are the constant 0).
 //
 // Replaces the reference's PrimeFieldElem (BigUint residue, `*` then `%`):
 //   src/building_block/field/prime_field_elem.rs:263-457   (reference paths are
@@ -62,16 +67,27 @@ ZKT_HD uint32_t subb(uint32_t a, uint32_t b, uint32_t& c) { unsigned co; uint32_
 // hands them s34 as scratch, and their callers keep their base pointer there (DESIGN §5 "A compiler limit"; tools/check_base_pointer.py flags exactly this).
 #define ZKT_FORCE_FRAME() do { alignas(64) volatile uint32_t zkt_frame_anchor_[16]; zkt_frame_anchor_[0] = 0u; } while (0)
 
+// Host check only (csrc/hostcheck.cpp defines ZKT_HOSTCHECK_LIMB_WATCH): the extremes of the limb intermediates of the lazy sum and difference passes, by channel
+// (hostcheck_fq30.h names them).  Everywhere else the macro is empty.
+#if defined(ZKT_HOSTCHECK_LIMB_WATCH) && !defined(__HIP_DEVICE_COMPILE__)
+struct LimbWatch { long long hi[4], lo[4]; LimbWatch() { for (int i = 0; i < 4; ++i) { hi[i] = -(1ll << 62); lo[i] = 1ll << 62; } } };
+inline LimbWatch& limb_watch() { static LimbWatch w; return w; }
+__attribute__((noinline)) inline void limb_watch_note(int ch, long long v) { LimbWatch& w = limb_watch(); if (v > w.hi[ch]) w.hi[ch] = v; if (v < w.lo[ch]) w.lo[ch] = v; }
+#define ZKT_LIMB_WATCH(ch, x) do { if constexpr (C::W == 30) limb_watch_note(ch, (long long)(x)); } while (0)      // the 30-bit layout only: every other field's passes stay as they are
+#else
+#define ZKT_LIMB_WATCH(ch, x) ((void)0)
+#endif
+
 template <class C> ZKT_HD Fp<C> fp_zero() { Fp<C> r;
 #pragma unroll
   for (int i = 0; i < C::N; ++i) r.v[i] = 0; return r; }
 template <class C> ZKT_HD Fp<C> fp_one() { Fp<C> r;   // Montgomery 1 = R mod p
 #pragma unroll
   for (int i = 0; i < C::N; ++i) r.v[i] = C::one(i); return r; }
-// W = 28: a lazily reduced value is zero iff it is one of 0, p, 2p, 3p.  The first limbs of
+// lazy limbs: a lazily reduced value is zero iff it is one of 0, p, 2p, 3p.  The first limbs of
 // those four differ from a random limb with probability 1 - 2^-26, so test limb 0 first.
 template <class C> ZKT_HD bool fp_is_zero(const Fp<C>& a) {
-  if constexpr (C::W == 28) {
+  if constexpr (C::W < 32) {
     const uint32_t a0 = a.v[0];
     if (!((a0 == C::kp(0, 0)) | (a0 == C::kp(1, 0)) | (a0 == C::kp(2, 0)) | (a0 == C::kp(3, 0)))) return false;
     uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
@@ -100,21 +116,25 @@ template <class C> ZKT_HD void fp_cond_sub(Fp<C>& r, uint32_t top) {
 // q = floor(v_top * QEST_M / 2^32) never exceeds floor(v/p) and is at most 3 below it for v < 12p
 // (checked exhaustively over the reachable top limbs in tests/test_hostcheck.py); the pass adds
 // q*(2^(WN) - p) limb by limb while propagating carries, and the 2^(WN) bit falls off the top.
+// W = 30.  v: limbs < 2^32 - 2^6 (v[i] + carry must not wrap: q <= 20 and t < 21 * 2^30 + 2^32 give carry < 2^5 + 4), value < 12p (fp_add: limbs < 2^31, value < 8p;
+// fp_sub: limbs <= 2^30 - 1 + max subk < 3 * 2^30, value < 12p).  Same result: limbs < 2^30, value < 4p (tests/test_fq30_hostcheck.py sweeps the top limbs).
 template <class C> ZKT_HD Fp<C> fp_lazy_reduce(const uint32_t* v) {
   constexpr uint32_t M = (1u << C::W) - 1;
   Fp<C> r; const uint32_t q = (uint32_t)(((uint64_t)v[C::N - 1] * C::QEST_M) >> 32);
   uint32_t carry = 0;
 #pragma unroll
   for (int i = 0; i < C::N; ++i) {
+    ZKT_LIMB_WATCH(0, (uint64_t)v[i] + carry);
     uint64_t t = (uint64_t)q * C::comp(i) + (uint64_t)(v[i] + carry);
     r.v[i] = (uint32_t)t & M; carry = (uint32_t)(t >> C::W);
+    ZKT_LIMB_WATCH(1, t); ZKT_LIMB_WATCH(3, carry);
   }
   return r;
 }
 
 // plus (prime_field_elem.rs:278-286)
 template <class C> ZKT_HD Fp<C> fp_add(const Fp<C>& a, const Fp<C>& b) {
-  if constexpr (C::W == 28) {
+  if constexpr (C::W < 32) {
     uint32_t v[C::N];
 #pragma unroll
     for (int i = 0; i < C::N; ++i) v[i] = a.v[i] + b.v[i];
@@ -127,12 +147,13 @@ template <class C> ZKT_HD Fp<C> fp_add(const Fp<C>& a, const Fp<C>& b) {
     return r;
   }
 }
-// minus (prime_field_elem.rs:288-300): a<b -> p-(b-a).  W = 28: a + 8p - b with 8p spread so no limb borrows.
+// minus (prime_field_elem.rs:288-300): a<b -> p-(b-a).  Lazy limbs: a + 8p - b with 8p spread so no limb borrows (every limb of subk but the top one is >= 2^W - 1,
+// the top one covers the top limb of any value < 4p).  W = 30: limbs of the sum <= 2^30 - 1 + max subk < 3 * 2^30, value < 12p.
 template <class C> ZKT_HD Fp<C> fp_sub(const Fp<C>& a, const Fp<C>& b) {
-  if constexpr (C::W == 28) {
+  if constexpr (C::W < 32) {
     uint32_t v[C::N];
 #pragma unroll
-    for (int i = 0; i < C::N; ++i) v[i] = a.v[i] + C::subk(i) - b.v[i];
+    for (int i = 0; i < C::N; ++i) { v[i] = a.v[i] + C::subk(i) - b.v[i]; ZKT_LIMB_WATCH(2, (long long)a.v[i] + C::subk(i) - b.v[i]); }
     return fp_lazy_reduce<C>(v);
   } else {
     Fp<C> r; uint32_t bw = 0;
@@ -145,8 +166,8 @@ template <class C> ZKT_HD Fp<C> fp_sub(const Fp<C>& a, const Fp<C>& b) {
   }
 }
 // negate (prime_field_elem.rs:448-457): 0 stays 0
-template <class C> ZKT_HD Fp<C> fp_neg(const Fp<C>& a) {
-  if constexpr (C::W == 28) {
+template <class C> ZKT_HD Fp<C> fp_neg(const Fp<C>& a) {      // lazy limbs: 8p - a by fp_sub (limbs <= max subk, value <= 8p)
+  if constexpr (C::W < 32) {
     return fp_sub(fp_zero<C>(), a);
   } else {
     Fp<C> r; uint32_t bw = 0;
@@ -159,7 +180,7 @@ template <class C> ZKT_HD Fp<C> fp_neg(const Fp<C>& a) {
   }
 }
 template <class C> ZKT_HD bool fp_eq(const Fp<C>& a, const Fp<C>& b) {
-  if constexpr (C::W == 28) {
+  if constexpr (C::W < 32) {
     return fp_is_zero(fp_sub(a, b));
   } else {
     uint32_t o = 0;
@@ -173,7 +194,9 @@ template <class C> ZKT_HD Fp<C> fp_dbl(const Fp<C>& a) { return fp_add(a, a); }
 //   fp_add3   a + b + c          limbs < 3*2^28, value < 12p
 //   fp_addsub a + b - c          a + b + 8p - c < 16p
 //   fp_subsub a - b - c          a + 16p - b - c < 20p (the 16p spread covers two subtrahend limbs)
+// (W = 30: a + b + subk - c and subk3 - b - c + a pass 2^32 in one limb; the G1 MSM object uses none of the three, so they are not provided there)
 template <class C> ZKT_HD Fp<C> fp_add3(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c) {
+  static_assert(C::W != 30, "three-term sums are not provided for 30-bit limbs");
   if constexpr (C::W == 28) {
     uint32_t v[C::N];
 #pragma unroll
@@ -182,6 +205,7 @@ template <class C> ZKT_HD Fp<C> fp_add3(const Fp<C>& a, const Fp<C>& b, const Fp
   } else return fp_add(fp_add(a, b), c);
 }
 template <class C> ZKT_HD Fp<C> fp_addsub(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c) {
+  static_assert(C::W != 30, "three-term sums are not provided for 30-bit limbs");
   if constexpr (C::W == 28) {
     uint32_t v[C::N];
 #pragma unroll
@@ -190,6 +214,7 @@ template <class C> ZKT_HD Fp<C> fp_addsub(const Fp<C>& a, const Fp<C>& b, const 
   } else return fp_sub(fp_add(a, b), c);
 }
 template <class C> ZKT_HD Fp<C> fp_subsub(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c) {
+  static_assert(C::W != 30, "three-term sums are not provided for 30-bit limbs");
   if constexpr (C::W == 28) {
     uint32_t v[C::N];
 #pragma unroll
@@ -199,48 +224,88 @@ template <class C> ZKT_HD Fp<C> fp_subsub(const Fp<C>& a, const Fp<C>& b, const 
 }
 // a - b - 2c in one reduction pass (the x-coordinate of every addition formula).  W = 28: a + 16p - b - 2c with 16p spread so that
 // no limb borrows (limbs < 2^31, value < 20p: the quotient estimate of fp_lazy_reduce still leaves < 4p, tests/test_hostcheck.py).
+// W = 30: a limb of the 16p spread must be >= 3 (2^30 - 1) to cover b + 2c, so a + subk3 - b - 2c passes 2^32.  The subtrahend side s = subk3 - b - 2c stays in a u32
+// (0 <= s <= max subk3 < 2^32) and meets a in the 64-bit sum of fp_lazy_reduce2; value < 4p + 16p = 20p < 2^390.
+template <class C> ZKT_HD Fp<C> fp_lazy_reduce2(const uint32_t* x, const uint32_t* s) {
+  static_assert(C::W == 30, "the 64-bit sum pass of the 30-bit limbs");
+  constexpr uint32_t M = (1u << C::W) - 1;
+  // x: limbs < 2^30; s: limbs < 2^32, top limbs small (x[N-1] + s[N-1] < 2^26: the top limb of a value < 20p).  q <= 20, so t < 21 * 2^30 + 2^32 + 2^6 < 2^35
+  // and the carry stays below 2^5.  Result: limbs < 2^30, value < 4p (the quotient estimate is fp_lazy_reduce's).
+  Fp<C> r; const uint32_t q = (uint32_t)(((uint64_t)(x[C::N - 1] + s[C::N - 1]) * C::QEST_M) >> 32);
+  uint32_t carry = 0;
+#pragma unroll
+  for (int i = 0; i < C::N; ++i) {
+    ZKT_LIMB_WATCH(0, (uint64_t)x[i] + carry);
+    uint64_t t = (uint64_t)q * C::comp(i) + (uint64_t)(x[i] + carry) + (uint64_t)s[i];
+    r.v[i] = (uint32_t)t & M; carry = (uint32_t)(t >> C::W);
+    ZKT_LIMB_WATCH(1, t); ZKT_LIMB_WATCH(3, carry);
+  }
+  return r;
+}
 template <class C> ZKT_HD Fp<C> fp_sub2(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c) {
   if constexpr (C::W == 28) {
     uint32_t v[C::N];
 #pragma unroll
     for (int i = 0; i < C::N; ++i) v[i] = a.v[i] + C::subk3(i) - b.v[i] - 2 * c.v[i];
     return fp_lazy_reduce<C>(v);
+  } else if constexpr (C::W == 30) {
+    uint32_t x[C::N], s[C::N];
+#pragma unroll
+    for (int i = 0; i < C::N; ++i) { x[i] = a.v[i]; s[i] = C::subk3(i) - b.v[i] - 2 * c.v[i]; ZKT_LIMB_WATCH(2, (long long)C::subk3(i) - b.v[i] - 2ll * c.v[i]); }
+    return fp_lazy_reduce2<C>(x, s);
   } else {
     return fp_sub(fp_sub(a, b), fp_dbl(c));
   }
 }
 
-// acc += a*b on one 64-bit column accumulator (W = 28 path): a single v_mad_u64_u32
+// acc += a*b on one 64-bit column accumulator (lazy-limb paths): a single v_mad_u64_u32
 ZKT_HD uint64_t mad64(uint32_t a, uint32_t b, uint64_t c) { return (uint64_t)a * b + c; }
+
+// W = 30: the mid-column carry hand-over.  Bit t of a column's mask (C::split_mul / split_sqr / split_mul2, generated) is set where the worst case of the running sum
+// (the carry of the column before, every operand limb 2^30 - 1, the limbs of p and of the 8p spread exact) would reach 2^64 with multiply-add t: there the bits above
+// 2^30 move to `hi` and the column goes on from its low 30 bits, which is all the reduction digit and the result limb read.  The column's carry is (acc >> 30) + hi
+// < 2^36.  No overflow: tests/test_fq30_hostcheck.py recomputes every column's worst case from the generated constants, with and without the splits.
+// W = 28 fields have no masks: the constant 0, and every line below folds away.
+template <class C> ZKT_HD constexpr uint64_t fp_split_mul(int k) { if constexpr (C::W == 30) return C::split_mul(k); else return 0; }
+template <class C> ZKT_HD constexpr uint64_t fp_split_sqr(int k) { if constexpr (C::W == 30) return C::split_sqr(k); else return 0; }
+template <class C> ZKT_HD constexpr uint64_t fp_split_mul2(int k) { if constexpr (C::W == 30) return C::split_mul2(k); else return 0; }
+template <int W> ZKT_HD void fp_split(uint64_t mask, int& t, uint64_t& acc, uint64_t& hi) {
+  if ((mask >> t) & 1) { hi += acc >> W; acc &= (1ull << W) - 1; }
+  ++t;
+}
 
 // Montgomery product a*b*R^-1 mod p.  times (prime_field_elem.rs:302-308) in the Montgomery domain.
 // W = 32: inputs and output in [0,p).
 // W = 28: inputs < 4p with limbs < 2^28; output (ab + mp)/R < p(1 + 16p/R) < 1.01p, limbs < 2^28.
 //         Column sums: 28 products < 2^56 plus a carry < 2^36 stay below 2^61.
+// W = 30: inputs < 4p with limbs < 2^30; output < p(1 + 16p/2^390) < 1.04p, limbs < 2^30.  Column sums: fp_split above.
 template <class C> ZKT_HD Fp<C> fp_mul_impl(const Fp<C>& a, const Fp<C>& b) {
   constexpr int N = C::N;
   Fp<C> r; uint32_t m[N];
-  if constexpr (C::W == 28) {
-    constexpr uint32_t M = (1u << 28) - 1;
+  if constexpr (C::W < 32) {
+    constexpr int W = C::W; constexpr uint32_t M = (1u << W) - 1;
     uint64_t acc = 0;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
+      const uint64_t sm = fp_split_mul<C>(k); uint64_t hi = 0; int t = 0;
 #pragma unroll
-      for (int i = 0; i <= k; ++i) acc = mad64(a.v[i], b.v[k - i], acc);
+      for (int i = 0; i <= k; ++i) { fp_split<W>(sm, t, acc, hi); acc = mad64(a.v[i], b.v[k - i], acc); }
 #pragma unroll
-      for (int j = 0; j < k; ++j) acc = mad64(m[j], C::mod(k - j), acc);
+      for (int j = 0; j < k; ++j) { fp_split<W>(sm, t, acc, hi); acc = mad64(m[j], C::mod(k - j), acc); }
       m[k] = ((uint32_t)acc * C::INV) & M;
+      fp_split<W>(sm, t, acc, hi);
       acc = mad64(m[k], C::mod(0), acc);
-      acc >>= 28;
+      acc = (acc >> W) + hi;
     }
 #pragma unroll
     for (int k = N; k < 2 * N; ++k) {
+      const uint64_t sm = fp_split_mul<C>(k); uint64_t hi = 0; int t = 0;
 #pragma unroll
-      for (int i = k - N + 1; i < N; ++i) acc = mad64(a.v[i], b.v[k - i], acc);
+      for (int i = k - N + 1; i < N; ++i) { fp_split<W>(sm, t, acc, hi); acc = mad64(a.v[i], b.v[k - i], acc); }
 #pragma unroll
-      for (int j = k - N + 1; j < N; ++j) acc = mad64(m[j], C::mod(k - j), acc);
+      for (int j = k - N + 1; j < N; ++j) { fp_split<W>(sm, t, acc, hi); acc = mad64(m[j], C::mod(k - j), acc); }
       r.v[k - N] = (uint32_t)acc & M;
-      acc >>= 28;
+      acc = (acc >> W) + hi;
     }
     return r;
   } else {
@@ -271,28 +336,31 @@ template <class C> ZKT_HD Fp<C> fp_mul_impl(const Fp<C>& a, const Fp<C>& b) {
 
 // W = 28 squaring: each cross product once against the pre-doubled operand (limbs < 2^29, so the
 // doubled products stay < 2^57 and a column still fits 64 bits): 105 + 196 MADs instead of 392.
+// W = 30: the doubled limbs are < 2^31, a cross product < 2^61; the column sums are those of the product (91 + 169 multiply-adds), the splits C::split_sqr.
 template <class C> ZKT_HD Fp<C> fp_sqr_impl(const Fp<C>& a) {
-  static_assert(C::W == 28, "lazy-limb fields only");
-  constexpr int N = C::N; constexpr uint32_t M = (1u << 28) - 1;
+  static_assert(C::W < 32, "lazy-limb fields only");
+  constexpr int N = C::N; constexpr int W = C::W; constexpr uint32_t M = (1u << W) - 1;
   Fp<C> r; uint32_t m[N], d[N]; uint64_t acc = 0;
 #pragma unroll
   for (int i = 0; i < N; ++i) d[i] = a.v[i] << 1;
 #pragma unroll
   for (int k = 0; k < 2 * N; ++k) {
+    const uint64_t sm = fp_split_sqr<C>(k); uint64_t hi = 0; int t = 0;
 #pragma unroll
-    for (int i = (k < N ? 0 : k - N + 1); 2 * i < k; ++i) acc = mad64(d[i], a.v[k - i], acc);
-    if ((k & 1) == 0) acc = mad64(a.v[k / 2], a.v[k / 2], acc);
+    for (int i = (k < N ? 0 : k - N + 1); 2 * i < k; ++i) { fp_split<W>(sm, t, acc, hi); acc = mad64(d[i], a.v[k - i], acc); }
+    if ((k & 1) == 0) { fp_split<W>(sm, t, acc, hi); acc = mad64(a.v[k / 2], a.v[k / 2], acc); }
     if (k < N) {
 #pragma unroll
-      for (int j = 0; j < k; ++j) acc = mad64(m[j], C::mod(k - j), acc);
+      for (int j = 0; j < k; ++j) { fp_split<W>(sm, t, acc, hi); acc = mad64(m[j], C::mod(k - j), acc); }
       m[k] = ((uint32_t)acc * C::INV) & M;
+      fp_split<W>(sm, t, acc, hi);
       acc = mad64(m[k], C::mod(0), acc);
     } else {
 #pragma unroll
-      for (int j = k - N + 1; j < N; ++j) acc = mad64(m[j], C::mod(k - j), acc);
+      for (int j = k - N + 1; j < N; ++j) { fp_split<W>(sm, t, acc, hi); acc = mad64(m[j], C::mod(k - j), acc); }
       r.v[k - N] = (uint32_t)acc & M;
     }
-    acc >>= 28;
+    acc = (acc >> W) + hi;
   }
   return r;
 }
@@ -301,27 +369,33 @@ template <class C> ZKT_HD Fp<C> fp_sqr_impl(const Fp<C>& a) {
 // borrow-safe spread of 8p, limbs < 2^29, so a column sums 14 products < 2^56, 14 < 2^57 and 14 reduction products < 2^56:
 // below 2^62.  Output (ab + c(8p-d) + mp)/R < p (1 + 48 p/R) < 1.04p.
 // SUB = false: a*b + c*d the same way (no spread needed).
+// W = 30: the spread limbs 8p - d are <= max subk < 2^31, a subtrahend product < 2^61; a column is cut once or twice (C::split_mul2, columns 4..19; the masks are those
+// of SUB = true and cover SUB = false, whose terms are smaller).  Output (ab + c(8p-d) + mp)/2^390 < p (1 + 48 p/2^390) < 1.1p, limbs < 2^30.
 template <class C, bool SUB> ZKT_HD Fp<C> fp_mul2_impl(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c, const Fp<C>& d) {
-  static_assert(C::W == 28, "lazy-limb fields only");
-  constexpr int N = C::N; constexpr uint32_t M = (1u << 28) - 1;
+  static_assert(C::W < 32, "lazy-limb fields only");
+  constexpr int N = C::N; constexpr int W = C::W; constexpr uint32_t M = (1u << W) - 1;
   Fp<C> r; uint32_t m[N], nd[N]; uint64_t acc = 0;
 #pragma unroll
   for (int i = 0; i < N; ++i) nd[i] = SUB ? C::subk(i) - d.v[i] : d.v[i];
 #pragma unroll
   for (int k = 0; k < 2 * N; ++k) {
+    const uint64_t sm = fp_split_mul2<C>(k); uint64_t hi = 0; int t = 0;
 #pragma unroll
-    for (int i = (k < N ? 0 : k - N + 1); i <= (k < N ? k : N - 1); ++i) { acc = mad64(a.v[i], b.v[k - i], acc); acc = mad64(c.v[i], nd[k - i], acc); }
+    for (int i = (k < N ? 0 : k - N + 1); i <= (k < N ? k : N - 1); ++i) {
+      fp_split<W>(sm, t, acc, hi); acc = mad64(a.v[i], b.v[k - i], acc); fp_split<W>(sm, t, acc, hi); acc = mad64(c.v[i], nd[k - i], acc);
+    }
     if (k < N) {
 #pragma unroll
-      for (int j = 0; j < k; ++j) acc = mad64(m[j], C::mod(k - j), acc);
+      for (int j = 0; j < k; ++j) { fp_split<W>(sm, t, acc, hi); acc = mad64(m[j], C::mod(k - j), acc); }
       m[k] = ((uint32_t)acc * C::INV) & M;
+      fp_split<W>(sm, t, acc, hi);
       acc = mad64(m[k], C::mod(0), acc);
     } else {
 #pragma unroll
-      for (int j = k - N + 1; j < N; ++j) acc = mad64(m[j], C::mod(k - j), acc);
+      for (int j = k - N + 1; j < N; ++j) { fp_split<W>(sm, t, acc, hi); acc = mad64(m[j], C::mod(k - j), acc); }
       r.v[k - N] = (uint32_t)acc & M;
     }
-    acc >>= 28;
+    acc = (acc >> W) + hi;
   }
   return r;
 }
@@ -361,7 +435,7 @@ template <class C> ZKT_HD void fp2_mul_kara(const Fp<C>& a0, const Fp<C>& a1, co
   }
 }
 
-// ---- paired products (W = 28): two independent Montgomery scans in ONE column loop ----------------------------------------------------------------
+// ---- paired products (lazy limbs): two independent Montgomery scans in ONE column loop ----------------------------------------------------------------
 // Inside one product the compiler does not keep `acc >>= 28; acc = mad64(a, b, acc)` as written: it starts every column from zero and adds the carry with a
 // 64-bit addition at the column's end (one v_lshl_add_u64 per column).  ZKT_PIN keeps a chain as written: an empty asm that owns the accumulator after every
 // multiply-add.  The compiler's hazard model assumes that a register written by inline asm may not be read by the very next instruction, so the pin of ONE chain
@@ -377,51 +451,56 @@ template <class C> ZKT_HD void fp2_mul_kara(const Fp<C>& a0, const Fp<C>& a1, co
 #endif
 ZKT_HD uint64_t mad64p(uint32_t a, uint32_t b, uint64_t c) { uint64_t r = (uint64_t)a * b + c; ZKT_PIN(r); return r; }
 
+// W = 30: both chains hand their carries over at the same multiply-add of the same columns (C::split_mul / split_sqr, as in the single scans).
 template <class C> ZKT_HD void fp_mul_pair_impl(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c, const Fp<C>& d, Fp<C>& ab, Fp<C>& cd) {
-  static_assert(C::W == 28, "lazy-limb fields only");
-  constexpr int N = C::N; constexpr uint32_t M = (1u << 28) - 1;
+  static_assert(C::W < 32, "lazy-limb fields only");
+  constexpr int N = C::N; constexpr int W = C::W; constexpr uint32_t M = (1u << W) - 1;
   Fp<C> r0, r1; uint32_t m0[N], m1[N]; uint64_t s = 0, t = 0;
 #pragma unroll
   for (int k = 0; k < 2 * N; ++k) {
+    const uint64_t sm = fp_split_mul<C>(k); uint64_t hs = 0, ht = 0; int n0 = 0, n1 = 0;
 #pragma unroll
-    for (int i = (k < N ? 0 : k - N + 1); i <= (k < N ? k : N - 1); ++i) { s = mad64p(a.v[i], b.v[k - i], s); t = mad64p(c.v[i], d.v[k - i], t); }
+    for (int i = (k < N ? 0 : k - N + 1); i <= (k < N ? k : N - 1); ++i) {
+      fp_split<W>(sm, n0, s, hs); s = mad64p(a.v[i], b.v[k - i], s); fp_split<W>(sm, n1, t, ht); t = mad64p(c.v[i], d.v[k - i], t);
+    }
     if (k < N) {
 #pragma unroll
-      for (int j = 0; j < k; ++j) { s = mad64p(m0[j], C::mod(k - j), s); t = mad64p(m1[j], C::mod(k - j), t); }
+      for (int j = 0; j < k; ++j) { fp_split<W>(sm, n0, s, hs); s = mad64p(m0[j], C::mod(k - j), s); fp_split<W>(sm, n1, t, ht); t = mad64p(m1[j], C::mod(k - j), t); }
       m0[k] = ((uint32_t)s * C::INV) & M; m1[k] = ((uint32_t)t * C::INV) & M;
-      s = mad64p(m0[k], C::mod(0), s); t = mad64p(m1[k], C::mod(0), t);
+      fp_split<W>(sm, n0, s, hs); s = mad64p(m0[k], C::mod(0), s); fp_split<W>(sm, n1, t, ht); t = mad64p(m1[k], C::mod(0), t);
     } else {
 #pragma unroll
-      for (int j = k - N + 1; j < N; ++j) { s = mad64p(m0[j], C::mod(k - j), s); t = mad64p(m1[j], C::mod(k - j), t); }
+      for (int j = k - N + 1; j < N; ++j) { fp_split<W>(sm, n0, s, hs); s = mad64p(m0[j], C::mod(k - j), s); fp_split<W>(sm, n1, t, ht); t = mad64p(m1[j], C::mod(k - j), t); }
       r0.v[k - N] = (uint32_t)s & M; r1.v[k - N] = (uint32_t)t & M;
     }
-    s >>= 28; t >>= 28;
+    s = (s >> W) + hs; t = (t >> W) + ht;
   }
   ab = r0; cd = r1;
 }
 // the squaring scan of fp_sqr_impl, twice
 template <class C> ZKT_HD void fp_sqr_pair_impl(const Fp<C>& a, const Fp<C>& c, Fp<C>& aa, Fp<C>& cc) {
-  static_assert(C::W == 28, "lazy-limb fields only");
-  constexpr int N = C::N; constexpr uint32_t M = (1u << 28) - 1;
+  static_assert(C::W < 32, "lazy-limb fields only");
+  constexpr int N = C::N; constexpr int W = C::W; constexpr uint32_t M = (1u << W) - 1;
   Fp<C> r0, r1; uint32_t m0[N], m1[N], d0[N], d1[N]; uint64_t s = 0, t = 0;
 #pragma unroll
   for (int i = 0; i < N; ++i) { d0[i] = a.v[i] << 1; d1[i] = c.v[i] << 1; }
 #pragma unroll
   for (int k = 0; k < 2 * N; ++k) {
+    const uint64_t sm = fp_split_sqr<C>(k); uint64_t hs = 0, ht = 0; int n0 = 0, n1 = 0;
 #pragma unroll
-    for (int i = (k < N ? 0 : k - N + 1); 2 * i < k; ++i) { s = mad64p(d0[i], a.v[k - i], s); t = mad64p(d1[i], c.v[k - i], t); }
-    if ((k & 1) == 0) { s = mad64p(a.v[k / 2], a.v[k / 2], s); t = mad64p(c.v[k / 2], c.v[k / 2], t); }
+    for (int i = (k < N ? 0 : k - N + 1); 2 * i < k; ++i) { fp_split<W>(sm, n0, s, hs); s = mad64p(d0[i], a.v[k - i], s); fp_split<W>(sm, n1, t, ht); t = mad64p(d1[i], c.v[k - i], t); }
+    if ((k & 1) == 0) { fp_split<W>(sm, n0, s, hs); s = mad64p(a.v[k / 2], a.v[k / 2], s); fp_split<W>(sm, n1, t, ht); t = mad64p(c.v[k / 2], c.v[k / 2], t); }
     if (k < N) {
 #pragma unroll
-      for (int j = 0; j < k; ++j) { s = mad64p(m0[j], C::mod(k - j), s); t = mad64p(m1[j], C::mod(k - j), t); }
+      for (int j = 0; j < k; ++j) { fp_split<W>(sm, n0, s, hs); s = mad64p(m0[j], C::mod(k - j), s); fp_split<W>(sm, n1, t, ht); t = mad64p(m1[j], C::mod(k - j), t); }
       m0[k] = ((uint32_t)s * C::INV) & M; m1[k] = ((uint32_t)t * C::INV) & M;
-      s = mad64p(m0[k], C::mod(0), s); t = mad64p(m1[k], C::mod(0), t);
+      fp_split<W>(sm, n0, s, hs); s = mad64p(m0[k], C::mod(0), s); fp_split<W>(sm, n1, t, ht); t = mad64p(m1[k], C::mod(0), t);
     } else {
 #pragma unroll
-      for (int j = k - N + 1; j < N; ++j) { s = mad64p(m0[j], C::mod(k - j), s); t = mad64p(m1[j], C::mod(k - j), t); }
+      for (int j = k - N + 1; j < N; ++j) { fp_split<W>(sm, n0, s, hs); s = mad64p(m0[j], C::mod(k - j), s); fp_split<W>(sm, n1, t, ht); t = mad64p(m1[j], C::mod(k - j), t); }
       r0.v[k - N] = (uint32_t)s & M; r1.v[k - N] = (uint32_t)t & M;
     }
-    s >>= 28; t >>= 28;
+    s = (s >> W) + hs; t = (t >> W) + ht;
   }
   aa = r0; cc = r1;
 }
@@ -449,28 +528,28 @@ template <class C> ZKT_HD Fp<C> fp_mulsub_fn(const Fp<C>& a, const Fp<C>& b, con
 template <class C> ZKT_HD Fp<C> fp_muladd_fn(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c, const Fp<C>& d) { return fp_mul2_impl<C, false>(a, b, c, d); }
 #endif
 template <class C> ZKT_HD Fp<C> fp_mulsub(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c, const Fp<C>& d) {
-  if constexpr (C::W == 28) return fp_mulsub_fn(a, b, c, d); else return fp_sub(fp_mul(a, b), fp_mul(c, d));
+  if constexpr (C::W < 32) return fp_mulsub_fn(a, b, c, d); else return fp_sub(fp_mul(a, b), fp_mul(c, d));
 }
 template <class C> ZKT_HD Fp<C> fp_muladd(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c, const Fp<C>& d) {
-  if constexpr (C::W == 28) return fp_muladd_fn(a, b, c, d); else return fp_add(fp_mul(a, b), fp_mul(c, d));
+  if constexpr (C::W < 32) return fp_muladd_fn(a, b, c, d); else return fp_add(fp_mul(a, b), fp_mul(c, d));
 }
 
 // Montgomery square.  sq (prime_field_elem.rs:330-335).  With 32-bit limbs a dedicated squaring
 // pays ~6 shift/add ops per column for the 96-bit doubling and does not win, so it is the product;
 // with 28-bit limbs the doubling is free (see fp_sqr_impl).
 template <class C> ZKT_HD Fp<C> fp_sqr(const Fp<C>& a) {
-  if constexpr (C::W == 28) return fp_sqr_fn(a); else return fp_mul(a, a);
+  if constexpr (C::W < 32) return fp_sqr_fn(a); else return fp_mul(a, a);
 }
 // (a b, c d) and (a^2, c^2): the interleaved scans in the device code of an object built with -DZKT_PAIR_MUL (W = 28), two ordinary calls everywhere else
 template <class C> ZKT_HD void fp_mul_pair(const Fp<C>& a, const Fp<C>& b, const Fp<C>& c, const Fp<C>& d, Fp<C>& ab, Fp<C>& cd) {
 #if defined(ZKT_PAIR_MUL) && defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (C::W == 28) { fp_mul_pair_impl(a, b, c, d, ab, cd); return; }
+  if constexpr (C::W < 32) { fp_mul_pair_impl(a, b, c, d, ab, cd); return; }
 #endif
   const Fp<C> r0 = fp_mul(a, b), r1 = fp_mul(c, d); ab = r0; cd = r1;
 }
 template <class C> ZKT_HD void fp_sqr_pair(const Fp<C>& a, const Fp<C>& c, Fp<C>& aa, Fp<C>& cc) {
 #if defined(ZKT_PAIR_MUL) && defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (C::W == 28) { fp_sqr_pair_impl(a, c, aa, cc); return; }
+  if constexpr (C::W < 32) { fp_sqr_pair_impl(a, c, aa, cc); return; }
 #endif
   const Fp<C> r0 = fp_sqr(a), r1 = fp_sqr(c); aa = r0; cc = r1;
 }
@@ -480,13 +559,14 @@ template <class C> ZKT_HD Fp<C> fp_from_words(const uint32_t* w) {
   Fp<C> x, r2;
 #pragma unroll
   for (int i = 0; i < C::N; ++i) r2.v[i] = C::r2(i);
-  if constexpr (C::W == 28) {
+  if constexpr (C::W < 32) {
+    constexpr int W = C::W;
 #pragma unroll
     for (int i = 0; i < C::N; ++i) {
-      const int lo = (28 * i) >> 5, sh = (28 * i) & 31;
+      const int lo = (W * i) >> 5, sh = (W * i) & 31;
       uint32_t t = w[lo] >> sh;
-      if (sh > 4 && lo + 1 < C::ABI_N) t |= w[lo + 1] << (32 - sh);
-      x.v[i] = t & 0x0fffffffu;
+      if (sh > 32 - W && lo + 1 < C::ABI_N) t |= w[lo + 1] << (32 - sh);
+      x.v[i] = t & ((1u << W) - 1);
     }
   } else {
 #pragma unroll
@@ -498,11 +578,12 @@ template <class C> ZKT_HD Fp<C> fp_from_words(const uint32_t* w) {
 template <class C> ZKT_HD void fp_to_words(const Fp<C>& a, uint32_t* w) {
   Fp<C> one = fp_zero<C>(); one.v[0] = 1;
   Fp<C> x = fp_mul(a, one);
-  if constexpr (C::W == 28) {
-    // x < 1.01p: one conditional subtraction makes it canonical
+  if constexpr (C::W < 32) {
+    // x < 1.01p (W = 30: < 1.04p): one conditional subtraction makes it canonical
+    constexpr int W = C::W;
     uint32_t s[C::N], bw = 0;
 #pragma unroll
-    for (int i = 0; i < C::N; ++i) { uint32_t t = x.v[i] - C::mod(i) - bw; bw = t >> 31; s[i] = t & 0x0fffffffu; }
+    for (int i = 0; i < C::N; ++i) { uint32_t t = x.v[i] - C::mod(i) - bw; bw = t >> 31; s[i] = t & ((1u << W) - 1); }
 #pragma unroll
     for (int i = 0; i < C::N; ++i) s[i] = bw ? x.v[i] : s[i];
 #pragma unroll
@@ -510,8 +591,8 @@ template <class C> ZKT_HD void fp_to_words(const Fp<C>& a, uint32_t* w) {
       uint32_t t = 0;
 #pragma unroll
       for (int i = 0; i < C::N; ++i) {
-        const int sft = 28 * i - 32 * j;
-        if (sft > -28 && sft < 32) t |= sft >= 0 ? (s[i] << (sft & 31)) : (s[i] >> ((-sft) & 31));
+        const int sft = W * i - 32 * j;
+        if (sft > -W && sft < 32) t |= sft >= 0 ? (s[i] << (sft & 31)) : (s[i] >> ((-sft) & 31));
       }
       w[j] = t;
     }
@@ -522,7 +603,7 @@ template <class C> ZKT_HD void fp_to_words(const Fp<C>& a, uint32_t* w) {
 }
 // W = 32 fields keep canonical values: an ABI word vector may be any 256-bit integer (PrimeFieldElem::new reduces e mod order,
 // prime_field_elem.rs:263-272).  2^256 < 3r and < 2p, 2n for the secp256k1 fields: two conditional subtractions reduce it.
-// (W = 28: fp_from_words needs no such step — the Montgomery product by R^2 accepts any 384-bit integer and returns its residue.)
+// (lazy limbs: fp_from_words needs no such step — the Montgomery product by R^2 accepts any 384-bit integer and returns its residue.)
 template <class C> ZKT_HD Fp<C> fp_canon32(Fp<C> x) {
   static_assert(C::W == 32, "canonical 32-bit-limb fields only");
   fp_cond_sub(x, 0); fp_cond_sub(x, 0);
@@ -709,7 +790,7 @@ template <class C> ZKT_HD void bgcd_inverse(uint32_t* io) {
 
 // In: a*R (Montgomery), non-zero.  Out: a^-1*R.
 // W = 32: the integer inverse of a*R is a^-1*R^-1; one Montgomery product with R^3 lifts it back.
-// W = 28: leave the Montgomery domain (canonical words), invert, re-enter.
+// lazy limbs: leave the Montgomery domain (canonical words), invert, re-enter.
 // Which loop: the word-step GCD for the 8-word fields everywhere, and for Fq in the objects built with -DZKT_WORDSTEP_INV_FQ (the MSM objects, where
 // fp_inv is called straight from a kernel).  In the tower / pairing objects Fq keeps the classic loop ON PURPOSE: there fp_inv sits below functions that
 // realign their stack (fq6_inv, fq12_inv, the final exponentiation: 64-byte aligned Fq6 temporaries) and keep their incoming stack pointer in s34, the
@@ -720,12 +801,12 @@ template <class C> ZKT_HD void fp_inverse_words(uint32_t* w) {
 #if defined(ZKT_WORDSTEP_INV_FQ)
   bgcd_inverse<C>(w);
 #else
-  if constexpr (C::W == 28) bgcd_inverse_classic<C>(w); else bgcd_inverse<C>(w);
+  if constexpr (C::W < 32) bgcd_inverse_classic<C>(w); else bgcd_inverse<C>(w);
 #endif
 }
 template <class C> ZKT_FN Fp<C> fp_inv(Fp<C> a) {
   uint32_t w[C::ABI_N];
-  if constexpr (C::W == 28) {
+  if constexpr (C::W < 32) {
     fp_to_words(a, w);
     fp_inverse_words<C>(w);
     return fp_from_words<C>(w);
@@ -754,6 +835,7 @@ template <class C> ZKT_FN Fp<C> fp_pow(Fp<C> a, const uint32_t* e, int nlimbs) {
 }
 
 typedef Fp<FqC> Fq;
+typedef Fp<Fq30C> Fq30;
 typedef Fp<FrC> FrE;
 typedef Fp<SpC> SpE;
 typedef Fp<SnC> SnE;

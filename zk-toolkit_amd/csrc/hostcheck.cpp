@@ -3,6 +3,7 @@
 // oracle without a GPU.  Not part of the product: libzkt_hip.so neither links nor calls
 // this, and the C ABI in include/zkt.h has no CPU path.  Built by __graft_entry__.build()
 // as zk-toolkit_amd/libzkt_hostcheck.so (hipcc --cuda-host-only).
+#define ZKT_HOSTCHECK_LIMB_WATCH      // fp.h: record the extremes of the lazy passes' limb intermediates (zkt_hostcheck_fq30_watch)
 #include "abi.h"
 #include <vector>
 #include "fq_program.h"
@@ -352,6 +353,9 @@ int zkt_hostcheck_ecdsa_sign(const uint8_t* digest, const uint32_t* d, const uin
 // ---- the paired Fq products and the paired mixed addition of the G1 accumulate loop: zkt_hostcheck_fq_pair, zkt_hostcheck_g1_acc.  Kept in a header of their
 // own so that the stand-alone sanitizer program (tests/c/acc_pairs_check.cpp) compiles them without the pairing code above.
 #include "hostcheck_acc_pairs.h"
+
+// ---- Fq on 13 x 30-bit limbs (fp.h, W = 30: the G1 MSM object's layout): products, sums, reductions, word conversions, inversion and the mixed addition on raw limbs
+#include "hostcheck_fq30.h"
 
 // ---- SHA-512 and Ed25519 (sha512.h, fe25519.h, ed25519.h): the per-message, per-key and per-signature functions the kernels of zkt_ed25519.hip run, on the host ----
 #include "ed25519.h"

@@ -26,17 +26,31 @@ namespace zkt {
 
 // The pipeline is generic over the group: G1 over Fq (FqOps), G2 over Fq2 (Fq2Ops, row f-1: eval_with_g2_hidings,
 // polynomial.rs:283-293) and secp256k1 (SpOps: (AffinePoints * PrimeFieldElems).sum(), secp256k1/affine_points.rs:25-31,123-144).
-// Coordinates are stored raw (Montgomery) with CW words each: affine point = 2*CW, XYZZ = 4*CW, Jacobian partial = 3*CW.
+// Coordinates are stored raw (Montgomery, in the limb layout of the object's field) with CW words each: affine point = 2*CW, XYZZ = 4*CW, Jacobian partial = 3*CW.
 // Kernels of the sort and reduce stages run beside the VALU-saturating accumulate waves of a neighbouring MSM; raise
 // their wave priority so their (few, latency-bound) instructions are not queued behind them.
 #ifndef ZKT_SIDE_PRIO
 #define ZKT_SIDE_PRIO __builtin_amdgcn_s_setprio(3)
 #endif
+// Words of a coordinate IN MEMORY (CW) are not the limbs of its field: the G1 object may run Fq on 13 x 30-bit limbs (Fq30C, -DZKT_FQ30) in the 14-word slots of
+// the 14 x 28 layout, so that every size the host code knows (table entries, bucket sums, the 42-word Jacobian partial of include/zkt.h) is the same for both.
+// A store writes the words past the limbs as zero; a load does not read them.
+template <class C> struct CoordMemWords { static constexpr int value = C::N; };
+template <> struct CoordMemWords<Fq30C> { static constexpr int value = FqC::N; };
+#if defined(ZKT_FQ30)
+typedef PrimeOps<Fq30C> G1Ops;
+#else
+typedef FqOps G1Ops;
+#endif
 template <class F> struct Coord;
 template <class C> struct Coord<PrimeOps<C>> {
-  static constexpr int CW = C::N;
+  static constexpr int CW = CoordMemWords<C>::value;
   __device__ static Fp<C> ld(const uint32_t* p) { return ld_raw<C>(p); }
-  __device__ static void st(uint32_t* p, const Fp<C>& a) { st_raw<C>(p, a); }
+  __device__ static void st(uint32_t* p, const Fp<C>& a) {
+    st_raw<C>(p, a);
+#pragma unroll
+    for (int i = C::N; i < CW; ++i) p[i] = 0u;
+  }
 };
 template <> struct Coord<Fq2Ops> {
   static constexpr int CW = 2 * FqC::N;
@@ -51,7 +65,7 @@ template <class F> __device__ inline void st_xy(uint32_t* p, const Xyzz<F>& a) {
   constexpr int CW = Coord<F>::CW;
   Coord<F>::st(p, a.X); Coord<F>::st(p + CW, a.Y); Coord<F>::st(p + 2 * CW, a.ZZ); Coord<F>::st(p + 3 * CW, a.ZZZ);
 }
-static int coord_words(int grp) { return grp == G_G1 ? FqC::N : grp == G_G2 ? 2 * FqC::N : SpC::N; }
+static int coord_words(int grp) { return grp == G_G1 ? Coord<G1Ops>::CW : grp == G_G2 ? Coord<Fq2Ops>::CW : Coord<SpOps>::CW; }      // memory words, not limbs
 // dimensions of the atomic-free partition sort (k_part_*, below): partitions of PART_SUB buckets, tiles of PART_TILE scalars, chunks of PART_CHUNK records
 static constexpr int PART_LO = 9, PART_SUB = 1 << PART_LO, PART_TPB = 256, PART_TILE = 4 * PART_TPB, PART_CHUNK = 8192, PART_MAXP = 2048;
 struct PartDims { uint32_t P, ntiles, maxblk; };
@@ -158,7 +172,7 @@ __global__ void __launch_bounds__(64) k_to_kernel_layout(const uint32_t* __restr
 // same for secp256k1; -DZKT_MSM_PART_OTHER instantiates G2 with a called multiply (an inlined Fq2 XYZZ add would be ~200 KB of code
 // and minutes of compile time).
 #if defined(ZKT_MSM_PART_G1)
-#define MSM_DISPATCH(grp, CALL) switch (grp) { case G_G1: { typedef FqOps F; CALL; } break; default: return hipErrorInvalidValue; }
+#define MSM_DISPATCH(grp, CALL) switch (grp) { case G_G1: { typedef G1Ops F; CALL; } break; default: return hipErrorInvalidValue; }
 #define PART(x) x##_g1
 #elif defined(ZKT_MSM_PART_SECP)     // secp256k1, multiply inlined like G1 (8-limb field: small code; a called multiply is latency bound at the low
 #define MSM_DISPATCH(grp, CALL) switch (grp) { case G_SECP: { typedef SpOps F; CALL; } break; default: return hipErrorInvalidValue; }   // occupancy of 2^17-term MSMs)
