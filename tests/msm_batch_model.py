@@ -1,4 +1,4 @@
-"""The batched MSM's plan and bucket layout (zk-toolkit_amd/csrc/zkt_msm.hip, msm_plan_batch / k_digits_batch) restated in numpy, on top of
+"""The batched MSM's plan and bucket layout (zk-toolkit_amd/csrc/zkt_msm_plan.cpp msm_plan_batch, msm_sort.h k_digits_batch) restated in numpy, on top of
 tests/msm_plan_model.py, plus the constructed scalar vectors of tests/test_gpu_msm_batch.py.
 
 TEST INFRASTRUCTURE, like msm_plan_model.py: it says which buckets a batch of scalar vectors fills, so that a GPU case can claim "vector v ends in the last

@@ -1,4 +1,4 @@
-"""A plain restatement of the MSM's host-side plan and digit scheme (zk-toolkit_amd/csrc/zkt_msm.hip), in numpy.
+"""A plain restatement of the MSM's host-side plan and digit scheme (zk-toolkit_amd/csrc/zkt_msm_plan.cpp, msm_sort.h, msm_ws.h), in numpy.
 
 TEST INFRASTRUCTURE.  This is not a simulator of the kernels: it says which window width, task size, sort and merge path a given
 scalar vector selects, so that a test can claim "this case reaches branch X" and have the claim checked on the CPU
@@ -7,20 +7,20 @@ thresholds below must update this file: test_msm_plan_model.py pins the model to
 import numpy as np
 
 # ---- thresholds, each restating one line of the library -------------------------------------------------------------------------
-HOT_NT = 512                # zkt_msm.hip, `static constexpr uint32_t HOT_NT = 512, HOT_CAP = 64, HOT_FAN = 64;` (k_task_scatter: nt > HOT_NT is hot)
+HOT_NT = 512                # msm_ws.h, `static constexpr uint32_t HOT_NT = 512, HOT_CAP = 64, HOT_FAN = 64;` (k_task_scatter: nt > HOT_NT is hot)
 HOT_CAP = 64                # same line: more than HOT_CAP hot buckets and the list is discarded (k_merge_hot returns, k_merge_partials does them all)
 HOT_FAN = 64                # same line: blocks per listed hot bucket in k_merge_hot
 MERGE_GROUP_MAX = 8         # msm_reduce_coop.h, k_merge_partials `constexpr uint32_t MERGE_GROUP_MAX = 8;` (2..8 pieces: one group; more: the block)
-SCATTER_LANE_MAX = 16       # zkt_msm.hip, k_task_scatter `if (nt <= 16)`: up to 16 tasks written by the bucket's lane, more by the whole block
+SCATTER_LANE_MAX = 16       # msm_sort.h, k_task_scatter `if (nt <= 16)`: up to 16 tasks written by the bucket's lane, more by the whole block
 RED_NG = 16                 # msm_reduce_coop.h, `RED_TPB = 64, RED_NG = RED_TPB / 4`
 BULK_MIN = 4 * RED_NG       # msm_reduce_coop.h, coop_block_sum `bulk = count > (size_t)4 * NG` (prime-field groups only: CoopBulk<PrimeOps>)
-PART_MIN_ENTRIES = 1 << 22  # zkt_msm.hip, launch_msm_sort `partition = (size_t)P.nwin * n >= (size_t(1) << 22)`
-PART_LO, PART_TPB, PART_CHUNK = 9, 256, 8192       # zkt_msm.hip, `PART_LO = 9, PART_SUB = 1 << PART_LO, PART_TPB = 256, PART_TILE = 4 * PART_TPB, PART_CHUNK = 8192, PART_MAXP = 2048`
+PART_MIN_ENTRIES = 1 << 22  # msm_sort.h, launch_sort `partition = (size_t)P.nwin * n >= (size_t(1) << 22)`
+PART_LO, PART_TPB, PART_CHUNK = 9, 256, 8192       # msm_ws.h, `PART_LO = 9, PART_SUB = 1 << PART_LO, PART_TPB = 256, PART_TILE = 4 * PART_TPB, PART_CHUNK = 8192, PART_MAXP = 2048`
 PART_SUB, PART_TILE, PART_MAXP = 1 << PART_LO, 4 * PART_TPB, 2048
 GRAPH_MAX_N = 1 << 19       # zkt_msm_handle.cpp, msm_submit `small = h.n < (size_t(1) << 19)`: a small resident set replays a captured graph
-CHUNK_MIN, CHUNK_MAX = 8, 128                       # zkt_msm.hip, pick_chunk: clamp to [8, MSM_CHUNK_MAX = 128]
+CHUNK_MIN, CHUNK_MAX = 8, 128                       # zkt_msm_plan.cpp, pick_chunk: clamp to [8, CHUNK = 128]
 TASK_LANES = {"g1": 196608, "secp": 196608, "g2": 65536}   # pick_chunk `tasks = grp == G_G2 ? 65536 : 196608`
-COORD_WORDS = {"g1": 14, "g2": 28, "secp": 8}      # zkt_msm.hip coord_words(): FqC::N = 14 limbs of 28 bits (zkt_constants.h), Fq2 twice that, SpC::N = 8
+COORD_WORDS = {"g1": 14, "g2": 28, "secp": 8}      # msm_ws.h coord_words(): FqC::N = 14 words (zkt_constants.h), Fq2 twice that, SpC::N = 8
 GROUPS = ("g1", "g2", "secp")
 FORMS = ("resident", "oneshot")
 

@@ -58,7 +58,7 @@ def test_r1cs_path_matches_reference_algorithm(L, case):
 def test_one_constraint_key_proves_again_after_device_memory_was_freed(L):
     """A one-constraint key has an EMPTY quotient base set (n - 1 = 0 terms): its zero-term MSM is captured as a graph like any other, and that graph must hold kernel
     nodes only — a runtime-owned memset node faults on the first replay after any later hipFree (graph replay).  The counters of a zero-term sort are cleared by
-    k_zero_words whatever their alignment (zkt_msm.hip zero_async; round-3 advisor finding): prove, free device memory elsewhere in the process, prove again — same proof."""
+    k_zero_words whatever their alignment (msm_sort.h zero_async; round-3 advisor finding): prove, free device memory elsewhere in the process, prove again — same proof."""
     import torch
     A, B, C, wit, l = chain_circuit(1)
     n, m = len(A), len(wit) - 1

@@ -1,4 +1,4 @@
-"""Every plan and bucket-merge branch of the MSM (zk-toolkit_amd/csrc/zkt_msm.hip, msm_reduce_coop.h) against python integers, for G1, G2 and
+"""Every plan and bucket-merge branch of the MSM (zk-toolkit_amd/csrc/zkt_msm_plan.cpp, msm_sort.h, zkt_msm.hip, msm_reduce_coop.h) against python integers, for G1, G2 and
 secp256k1, resident (zkt_*_bases_from_device + zkt_*_msm_dev twice + submit/collect on two slots) and one-shot (zkt_*_msm).
 
 The cases are built by tests/msm_plan_model.py, whose census of the scalars says which branch each case reaches — the hot-bucket boundary

@@ -56,6 +56,41 @@ def test_model_is_pinned_to_the_library_workspace_size():
         assert L.zkt_g1_msm_workspace_bytes(n) == M.g1_resident_workspace_bytes(n), n
 
 
+GROUP_ID = {"g1": 0, "g2": 1, "secp": 2}                  # zkt_internal.h, GroupId
+CARVE_PTRS = 27                                           # hostcheck.cpp, zkt_hostcheck_msm_carve: the first six are used at 256-byte alignment, the rest as words
+CARVE_ALIGN = (256,) * 6 + (4,) * (CARVE_PTRS - 6)
+
+
+def test_the_carve_ends_inside_the_workspace_of_every_plan():
+    """The plans sum their ws_bytes by hand (zkt_msm_plan.cpp: msm_plan, msm_plan_direct) while carve() hands the workspace out: in the host build of that file, the
+    carve's end lies inside ws_bytes and every pointer is aligned for its use, for all groups and forms; and the model restates ws_bytes for every group, not G1 only."""
+    import ctypes
+    H = ctypes.CDLL(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "zk-toolkit_amd", "libzkt_hostcheck.so"))
+    H.zkt_hostcheck_msm_ws_bytes.restype = H.zkt_hostcheck_msm_carve.restype = ctypes.c_size_t
+    H.zkt_hostcheck_msm_ws_bytes.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    H.zkt_hostcheck_msm_carve.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
+    offs = (ctypes.c_size_t * CARVE_PTRS)()
+    null = ctypes.c_size_t(-1).value
+    sizes = sorted(set(M.RESIDENT_STEPS) | set(M.ONESHOT_STEPS) | set(PIN_N) | {1, 2, 3, (1 << 20) + 1, 1 << 22})
+    runs = [(form, n, 0) for form in (0, 1) for n in sizes] + [(2, n, k) for n in (1, 1024, 16384, 1 << 17) for k in (1, 2, 31, 32)]
+    default_widths = not os.environ.get("ZKT_MSM_C")      # the library reads the width override once per process; the model restates the default plan
+    least = {}
+    for group in M.GROUPS:
+        for form, n, k in runs:
+            ws = H.zkt_hostcheck_msm_ws_bytes(n, GROUP_ID[group], form, k)
+            end = H.zkt_hostcheck_msm_carve(n, GROUP_ID[group], form, k, offs)
+            assert end <= ws, (group, form, n, k, end, ws)
+            for i, (o, a) in enumerate(zip(offs, CARVE_ALIGN)):
+                assert o == null or (o % a == 0 and o < end), (group, form, n, k, i, o)
+            assert all(o != null for o in offs[:4]) and (offs[4] == null) == (form == 2), (group, form, n, k)
+            if form == 1 or (form == 0 and default_widths):      # (msm_plan_direct does not read the override)
+                assert ws == M.plan(n, group, M.FORMS[form])["ws_bytes"], (group, form, n)
+            if form not in least or ws - end < least[form][0]:
+                least[form] = (ws - end, ("resident", "direct", "batch")[form], group, n, k)
+    for slack in least.values():      # (the batched plan takes its size from the carve plus 4096: its slack is that constant)
+        print("smallest slack between the carve's end and ws_bytes: %d bytes (%s form, %s, n = %d, k = %d)" % slack)
+
+
 def test_plan_steps_cover_every_combination_the_plan_can_pick():
     for form in M.FORMS:
         cand = {1}

@@ -427,3 +427,24 @@ int zkt_hostcheck_ed25519_verify(const uint8_t* msg, size_t len, const uint8_t* 
   return ed25519_verify_one<1>(msg, len, sig, pub, ed25519_comb_table(), tab) ? 1 : 0;
 }
 }  // extern "C"
+
+// ---- the MSM's plans against the carve-up of their workspace (msm_ws.h, zkt_msm_plan.cpp: the library's own host code) ----
+#include "msm_ws.h"
+namespace {
+// form 0: msm_plan (resident), 1: msm_plan_direct (one-shot), 2: msm_plan_batch of k vectors
+MsmPlan hostcheck_msm_plan(size_t n, int grp, int form, int k) { return form == 0 ? msm_plan(n, grp) : form == 1 ? msm_plan_direct(n, grp) : msm_plan_batch(n, grp, k); }
+}  // namespace
+extern "C" {
+size_t zkt_hostcheck_msm_ws_bytes(size_t n, int grp, int form, int k) { return hostcheck_msm_plan(n, grp, form, k).ws_bytes; }
+// The carve of that plan over a 256-byte-aligned base: returns the offset of its end, and in offs[0..27) the offset of every pointer it hands out (~0 for one it
+// leaves null), in the order entries, slot, sums, order, rec, subhist (used at 256-byte alignment), then counts, cursor, size_hist, size_off, size_cur, hot,
+// offsets, colsum, rowsum, clsA, clsB, win_jac, scan_tmp, ntask, task_off, partial, hot_part, tilehist, tileoff, blkoff, part_scan (words).
+size_t zkt_hostcheck_msm_carve(size_t n, int grp, int form, int k, size_t* offs) {
+  alignas(256) static uint8_t base[256];      // only its address is used: the carve computes pointers and touches nothing
+  const MsmWs w = carve(hostcheck_msm_plan(n, grp, form, k), base);
+  const void* p[] = {w.entries, w.slot, w.sums, w.order, w.rec, w.subhist, w.counts, w.cursor, w.size_hist, w.size_off, w.size_cur, w.hot, w.offsets, w.colsum, w.rowsum,
+                     w.clsA, w.clsB, w.win_jac, w.scan_tmp, w.ntask, w.task_off, w.partial, w.hot_part, w.tilehist, w.tileoff, w.blkoff, w.part_scan};
+  for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i) offs[i] = p[i] ? (size_t)((const uint8_t*)p[i] - base) : ~(size_t)0;
+  return (size_t)(w.end - base);
+}
+}  // extern "C"

@@ -292,7 +292,7 @@ __global__ void __launch_bounds__(RED_TPB) ZKT_RED_ATTR k_marginals(const uint32
 // Bit classes of both weighted sums: class `bit` of A = sum of the column sums whose weight lo + 1 has that bit, class `bit` of B = sum of the row pieces
 // whose weight hi = index / RS has it.  The members of a class are ENUMERATED (the q-th weight with bit `bit` set is q with a one inserted at
 // that position), so no lane walks the non-members; every class is cut into WB_SPLIT blocks (cls[(bit * WB_SPLIT + part)]), which k_combine adds up.
-static constexpr int WB_TPB = 128, WB_NG = WB_TPB / 4, WB_SPLIT = 4;
+static constexpr int WB_TPB = 128, WB_NG = WB_TPB / 4;                // (WB_SPLIT: msm_ws.h, the workspace is sized by it)
 __device__ inline uint32_t insert_one(uint32_t q, int bit) { return ((q >> bit) << (bit + 1)) | (1u << bit) | (q & ((1u << bit) - 1u)); }
 template <class F>
 __global__ void __launch_bounds__(WB_TPB) ZKT_RED_ATTR k_weight_bits(const uint32_t* __restrict__ colsum, size_t NLO, int nbA,

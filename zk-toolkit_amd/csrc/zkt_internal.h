@@ -147,7 +147,7 @@ hipError_t launch_ed25519_sign(const uint8_t* msgs, const unsigned long long* of
 hipError_t launch_ed25519_verify(const uint8_t* msgs, const unsigned long long* off, const uint8_t* sigs, const uint8_t* pub, const uint32_t* btab, size_t n, uint32_t* ok,
                                  hipStream_t s);
 
-// ---- MSM (zkt_msm.hip), generic over the group (G_G1, G_G2, G_SECP) ------------------------------------------
+// ---- MSM, generic over the group (G_G1, G_G2, G_SECP): plans in zkt_msm_plan.cpp, kernels and their launchers in zkt_msm.hip (one object per group), these entry points in zkt_msm_dispatch.cpp ----
 struct MsmPlan {
   size_t n;            // terms
   int grp;             // GroupId

@@ -7,8 +7,8 @@
 // the waves to schedule.  Measured on MI355X, 2^20-term G2 MSM over resident bases: accumulate 10.97 -> 9.2 ms, whole MSM
 // 11.8 -> 9.95 ms.  Forcing two waves per SIMD (ZKT_G2PAIR_ATTR = amdgpu_waves_per_eu(2,2)) spills 560 B per lane, is not faster
 // (9.4 ms) and starves the reduce-stage kernels of registers, so it is not the default.
-// Memory layouts (window-multiple table, bucket sums, partials) are exactly those of the one-lane kernels in zkt_msm.hip, which
-// still do the table build and the reduction.
+// Memory layouts (window-multiple table, bucket sums, partials) are exactly those of the G2 kernels in zkt_msm.hip (Coord<Fq2Ops>), which
+// do the table build and the reduction; this kernel is the only G2 accumulate (the one-lane k_accumulate is instantiated for G1 and secp256k1 only).
 //
 // The split layout redefines zkt::Fq2, so this translation unit keeps its symbols in a namespace of its own.
 #define ZKT_FQ2_SPLIT
@@ -26,7 +26,7 @@ __device__ inline void st_half(uint32_t* p, const Fq2& a) { uint32_t* q = p + (f
 #pragma unroll
   for (int i = 0; i < FqC::N; ++i) q[i] = a.h.v[i]; }
 
-// same task list, same entry order, same memory layout as k_accumulate<Fq2Ops> (zkt_msm.hip); lanes 2t and 2t+1 share task t
+// the task list, entry order and memory layout the sort and reduce stages use for every group (k_accumulate, zkt_msm.hip); lanes 2t and 2t+1 share task t
 #ifndef ZKT_G2PAIR_ATTR
 #define ZKT_G2PAIR_ATTR
 #endif
