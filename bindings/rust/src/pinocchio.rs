@@ -158,4 +158,39 @@ impl Verifier {
         let io = Fr::flatten(&witness_io.to_dense());
         check_bool(unsafe { ffi::zkt_pinocchio_verify(&view, &pv, io.as_ptr()) })
     }
+    /// `verify` for every proof of a batch against one resident key (zkt_pinocchio_verify_batch): `Ok(accept)` per proof, or `Err(status)` where the reference's
+    /// `verify` panics (a pairing argument at infinity, `ZKT_ERR_INFINITY`).  `witness_io[i]` holds the io wires of proof i, the key's `n_io` values each.
+    pub fn verify_batch(&self, proofs: &[Proof], vk: &VerificationKey, witness_io: &[SparseVec<Bls12R>]) -> Vec<Result<bool, i32>> {
+        assert_eq!(proofs.len(), witness_io.len());
+        let n = proofs.len();
+        // struct of arrays: g1 = v_mid_s | g1_w_mid_s | y_mid_s | alpha_v_mid_s | alpha_w_mid_s | alpha_y_mid_s | beta_vwy_mid_s (n each), g2 = g2_w_mid_s | h_s
+        let col1 = |f: &dyn Fn(&Proof) -> &G1Point| proofs.iter().map(|p| f(p).to_raw()).collect::<Vec<zkt_g1_affine>>();
+        let col2 = |f: &dyn Fn(&Proof) -> &G2Point| proofs.iter().map(|p| f(p).to_raw()).collect::<Vec<zkt_g2_affine>>();
+        let mut g1: Vec<zkt_g1_affine> = [col1(&|p| &p.v_mid_s), col1(&|p| &p.g1_w_mid_s), col1(&|p| &p.y_mid_s), col1(&|p| &p.alpha_v_mid_s), col1(&|p| &p.alpha_w_mid_s),
+                                          col1(&|p| &p.alpha_y_mid_s), col1(&|p| &p.beta_vwy_mid_s)].concat();
+        let mut g2: Vec<zkt_g2_affine> = [col2(&|p| &p.g2_w_mid_s), col2(&|p| &p.h_s)].concat();
+        let (p1, p2) = (g1.as_mut_ptr(), g2.as_mut_ptr());
+        let pv = unsafe { zkt_pinocchio_proof { v_mid_s: p1, g1_w_mid_s: p1.add(n), g2_w_mid_s: p2, y_mid_s: p1.add(2 * n), h_s: p2.add(n), alpha_v_mid_s: p1.add(3 * n),
+                                                alpha_w_mid_s: p1.add(4 * n), alpha_y_mid_s: p1.add(5 * n), beta_vwy_mid_s: p1.add(6 * n) } };
+        let mut io: Vec<u64> = Vec::with_capacity(n * vk.n_io * 4);
+        for w in witness_io { let d = w.to_dense(); assert_eq!(d.len(), vk.n_io); io.extend(Fr::flatten(&d)); }
+        let mut verdict = vec![0i32; n];
+        check(unsafe { ffi::zkt_pinocchio_verify_batch(vk.vk, &pv, if vk.n_io == 0 { std::ptr::null() } else { io.as_ptr() }, n, verdict.as_mut_ptr()) });
+        verdict.iter().map(|v| if *v < 0 { Err(-*v) } else { Ok(*v == 1) }).collect()
+    }
 }
+/// the verifier's side of a deployment that checks many proofs against one CRS: the verification key (crs.rs:24-39) stays in HBM with the line tables of its
+/// five G2 points and the tables of its io points (zkt_pinocchio_vk).  At most 12 io wires.
+pub struct VerificationKey { vk: *mut ffi::zkt_pinocchio_vk, n_io: usize }
+unsafe impl Send for VerificationKey {}
+impl VerificationKey {
+    pub fn new(crs: &CRS) -> Self {
+        init();
+        let mut buf = CrsBuf::from_crs(crs);
+        let view = buf.view(crs.n, crs.n_io(), crs.n_mid(), crs.max_degree);
+        let mut vk = std::ptr::null_mut();
+        check(unsafe { ffi::zkt_pinocchio_vk_create(&view, &mut vk) });
+        VerificationKey { vk, n_io: crs.n_io() }
+    }
+}
+impl Drop for VerificationKey { fn drop(&mut self) { unsafe { ffi::zkt_pinocchio_vk_free(self.vk) } } }

@@ -395,6 +395,25 @@ void zkt_pinocchio_pk_free(zkt_pinocchio_pk* pk);
  * tables of the key's io points are built on first sight of a key (~30 ms) and kept for the last two keys, a verification then takes
  * ~6.5 ms; calls are serialised inside the library. */
 int zkt_pinocchio_verify(const zkt_pinocchio_crs* crs, const zkt_pinocchio_proof* proof, const uint64_t* io_wires);
+/* The verifier with the verification key resident, n proofs per call (Verifier::verify pinocchio/verifier.rs:31-85 once per proof, against ONE
+ * VerificationKeys, crs.rs:24-39).  zkt_pinocchio_vk_create reads n_io, one_g2, alpha_v, alpha_w, alpha_y, gamma, beta_gamma, t, vk_io, wk_io, yk_io of the
+ * CRS and nothing else, and copies them: the handle does not depend on the caller's buffers afterwards.  ZKT_ERR_SHAPE for a missing pointer and for
+ * n_io > 12 (the fixed-base and window tables of a key's io points take twelve points); n_io == 0 is legal.  The handle keeps in HBM the 68 line triples
+ * of each of the five key G2 points — seven of the eleven G2 arguments of verifier.rs:43-84 are key constants, so a proof runs 3 G2 chains, reads 11 line
+ * streams and takes 5 final exponentiations — the tables of the three io point sets, alpha_w, t, and a verdict word on the key's points (every G2 point
+ * finite, on E' and in G2; alpha_w and t finite, on E and in G1; every io point at infinity or in its group).  A key that fails one of these tests is still
+ * a valid handle: its proofs are decided by the table-free kernels zkt_pinocchio_verify falls back to, with the same decisions.
+ * zkt_pinocchio_verify_batch: `proofs` is ONE zkt_pinocchio_proof whose nine pointers each address n consecutive points (struct of arrays); io_wires is
+ * n x n_io x 4 limbs, used as the 256-bit integers they are (verifier.rs:70-76), NULL only when n_io == 0.  verdict[i] is what zkt_pinocchio_verify returns
+ * for proof i: 1 accept, 0 reject, -ZKT_ERR_INFINITY where the reference panics; the five equalities are decided in the reference's order (verifier.rs:43-48,
+ * 51-55, 56-60, 61-65, 68-84), a rejection by an earlier one wins over a panic of a later one, and one proof never changes another's verdict or the call's
+ * status.  Returns ZKT_OK (also for n == 0), ZKT_ERR_SHAPE or ZKT_ERR_DEVICE.  Blocking, host pointers; a handle serves one call at a time (its own lock,
+ * different handles do not wait for each other on the host).  zkt_verify_set_fail_closed applies as in every verification entry point.  A handle owns its
+ * device memory: zkt_shutdown leaves it intact, zkt_pinocchio_vk_free releases it. */
+typedef struct zkt_pinocchio_vk zkt_pinocchio_vk;
+int zkt_pinocchio_vk_create(const zkt_pinocchio_crs* crs, zkt_pinocchio_vk** out);
+void zkt_pinocchio_vk_free(zkt_pinocchio_vk* vk);
+int zkt_pinocchio_verify_batch(zkt_pinocchio_vk* vk, const zkt_pinocchio_proof* proofs, const uint64_t* io_wires, size_t n, int32_t* verdict);
 
 /* a18: Bulletproofs::inner_product_argument bulletproofs.rs:19-55 over secp256k1; n a power of two; a, b are 4-limb
  * residues mod the group order; xs = one challenge per level (the reference draws them at bulletproofs.rs:42).

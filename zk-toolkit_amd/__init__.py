@@ -62,6 +62,9 @@ def lib():
         sz = ctypes.c_size_t
         L.zkt_pairing_product_check_batch.argtypes = [vp, vp, vp, sz, sz, vp]
         L.zkt_pinocchio_prove.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+        L.zkt_pinocchio_vk_create.argtypes = [vp, vp]
+        L.zkt_pinocchio_vk_free.argtypes = [vp]; L.zkt_pinocchio_vk_free.restype = None
+        L.zkt_pinocchio_verify_batch.argtypes = [vp, vp, vp, sz, vp]
         L.zkt_bls_hash_to_g2_batch.argtypes = [vp, vp, sz, vp]
         L.zkt_bls_sign_batch.argtypes = [vp, vp, vp, sz, vp]
         L.zkt_bls_public_keys_batch.argtypes = [vp, sz, vp]
