@@ -549,7 +549,8 @@ int zkt_groth16_setup_r1cs(size_t n, size_t l, size_t m, const zkt_sparse_rows* 
 /* Prover::prove (prover.rs:96-147), r and s injected; wires = a_0..a_m, 4-limb canonical Fr on the host. */
 int zkt_groth16_prove_r1cs(zkt_groth16_pk* pk, const uint64_t* wires, const uint64_t* r, const uint64_t* s,
                            zkt_g1_affine* A, zkt_g2_affine* B, zkt_g1_affine* C);
-/* the same with the wires already in HBM (device pointer) */
+/* the same with the wires already in HBM (device pointer).  zkt_groth16_prove_r1cs_dev, _submit and _partials take no stream: they read dev_wires on the key's
+ * own non-blocking stream, ordered behind no stream of the caller's, so the wires must be complete (their producing stream or event waited for) before the call. */
 int zkt_groth16_prove_r1cs_dev(zkt_groth16_pk* pk, const uint64_t* dev_wires, const uint64_t* r, const uint64_t* s,
                                zkt_g1_affine* A, zkt_g2_affine* B, zkt_g1_affine* C);
 /* Pipelined form: two proofs in flight on one (unsharded) key, the Fr stage of the next proof under the MSMs of the current one.
