@@ -448,3 +448,10 @@ size_t zkt_hostcheck_msm_carve(size_t n, int grp, int form, int k, size_t* offs)
   return (size_t)(w.end - base);
 }
 }  // extern "C"
+
+// ---- the layout of a host-pointer call's staging slots (host_stage.h: the library's own host code) ----
+#include "host_stage.h"
+extern "C" {
+int zkt_hostcheck_stage_slots() { return STAGE_SLOTS; }
+size_t zkt_hostcheck_stage_layout(const size_t* bytes, int count, size_t* offsets) { return stage_layout(bytes, count, offsets); }
+}  // extern "C"

@@ -1,10 +1,10 @@
-// C ABI (include/zkt.h) over the HIP kernels.  Host-pointer entry points stage through
-// a grow-only device arena; `_dev` entry points launch on the caller's stream.  There is
+// C ABI (include/zkt.h) over the HIP kernels: init and shutdown, fields, towers, groups, pairings and the one-shot MSM.  Host-pointer entry points stage
+// through a grow-only device arena, one Stage (host_stage.h) per call; `_dev` entry points launch on the caller's stream.  There is
 // no CPU compute path in this file: without a device every entry point fails.
-// The resident-base MSM handle (zkt_*_bases_*, zkt_*_msm_submit / _collect / _dev, zkt_*_msm_batch_*) is zkt_msm_handle.cpp.
+// The resident-base MSM handle (zkt_*_bases_*, zkt_*_msm_submit / _collect / _dev, zkt_*_msm_batch_*) is zkt_msm_handle.cpp; the hash and signature
+// entry points (zkt_sha256 / sha512 / ecdsa / ed25519_*) are zkt_hashsig.cpp.
 #include <hip/hip_runtime.h>
 #include <mutex>
-#include <vector>
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +12,7 @@
 #include "zkt_internal.h"
 #include "zkt_constants.h"
 #include "host_abi.h"
+#include "host_stage.h"
 static_assert(ZKT_G1_PARTIAL_WORDS == 3 * zkt::FqC::N && ZKT_G2_PARTIAL_WORDS == 6 * zkt::FqC::N && ZKT_SECP_PARTIAL_WORDS == 3 * zkt::SpC::N,
               "include/zkt.h partial sizes follow the internal limb layout");
 
@@ -40,7 +41,7 @@ int ensure_ready() {
   return hipSetDevice(g.device) == hipSuccess ? ZKT_OK : ZKT_ERR_DEVICE;
 }
 
-// grow-only staging arena (caller holds g.mu)
+// grow-only staging arena (caller holds g.mu: Stage::commit)
 int arena_reserve(size_t bytes) {
   if (bytes <= g.arena_bytes) return ZKT_OK;
   if (g.arena) { HIPCHK(hipFree(g.arena)); g.arena = nullptr; g.arena_bytes = 0; }
@@ -49,12 +50,9 @@ int arena_reserve(size_t bytes) {
   g.arena_bytes = want;
   return ZKT_OK;
 }
-struct Carver {
-  uint8_t* p; size_t off = 0;
-  explicit Carver(uint8_t* base) : p(base) {}
-  template <class T> T* take(size_t bytes) { off = (off + 255) & ~size_t(255); T* r = (T*)(p + off); off += bytes; return r; }
-};
-size_t padded(size_t b) { return (b + 255) & ~size_t(255); }
+size_t padded(size_t b) { return (b + 255) & ~size_t(255); }      // the blob of msm_host
+// the point at infinity in the ABI layout of a w-byte point: all zero, flag word 1
+void set_infinity(void* out, size_t w) { memset(out, 0, w); ((uint32_t*)out)[w / 4 - 2] = 1; }
 
 int reset_err(hipStream_t s) {
   unsigned long long v = NO_ERR;
@@ -74,20 +72,12 @@ template <class Launch>
 int staged_raw(const void* a, size_t a_total, const void* b, size_t b_total, void* out, size_t out_total, int err_code, Launch launch) {
   if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
   if (!a || !out || (b_total && !b)) return ZKT_ERR_SHAPE;
-  std::lock_guard<std::mutex> lk(g.mu);
-  HIPCHK(hipSetDevice(g.device));
-  int rc = arena_reserve(padded(a_total) + padded(b_total) + padded(out_total) + 1024);
-  if (rc) return rc;
-  Carver cv(g.arena);
-  uint32_t* da = cv.take<uint32_t>(a_total);
-  uint32_t* db = b_total ? cv.take<uint32_t>(b_total) : nullptr;
-  uint32_t* dout = cv.take<uint32_t>(out_total);
-  HIPCHK(hipMemcpyAsync(da, a, a_total, hipMemcpyHostToDevice, g.stream));
-  if (db) HIPCHK(hipMemcpyAsync(db, b, b_total, hipMemcpyHostToDevice, g.stream));
-  if ((rc = reset_err(g.stream))) return rc;
-  HIPCHK(launch(da, db, dout, g.stream));
-  HIPCHK(hipMemcpyAsync(out, dout, out_total, hipMemcpyDeviceToHost, g.stream));
-  return fetch_err(g.stream, err_code);
+  Stage st;
+  const int ia = st.in(a, a_total), ib = b_total ? st.in(b, b_total) : Stage::NONE, io = st.out(out, out_total);
+  ZCHK(st.commit());
+  ZCHK(reset_err(g.stream));
+  HIPCHK(launch(st.ptr<uint32_t>(ia), st.ptr<uint32_t>(ib), st.ptr<uint32_t>(io), g.stream));
+  return st.finish_err(err_code);
 }
 // elementwise form: fixed bytes per element
 template <class Launch>
@@ -123,17 +113,11 @@ int fp_sum(int field, const uint64_t* a, size_t n, uint64_t* out) {
   if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
   if (n == 0 || !a || !out) return ZKT_ERR_SHAPE;                    // assert!(self.0.len() > 0)
   const size_t w = field_bytes(field);
-  std::lock_guard<std::mutex> lk(g.mu);
-  HIPCHK(hipSetDevice(g.device));
-  int rc = arena_reserve(padded(w * n) + padded(w * (1 + fp_sum_scratch_elems())) + 1024);
-  if (rc) return rc;
-  Carver cv(g.arena);
-  uint32_t* da = cv.take<uint32_t>(w * n); uint32_t* dout = cv.take<uint32_t>(w * (1 + fp_sum_scratch_elems()));
-  HIPCHK(hipMemcpyAsync(da, a, w * n, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(launch_fp_sum(field, da, n, dout, dout + w / 4, g.stream));
-  HIPCHK(hipMemcpyAsync(out, dout, w, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return ZKT_OK;
+  Stage st;
+  const int ia = st.in(a, w * n), io = st.out(out, w), ip = st.scratch(w * fp_sum_scratch_elems());
+  ZCHK(st.commit());
+  HIPCHK(launch_fp_sum(field, st.ptr<uint32_t>(ia), n, st.ptr<uint32_t>(io), st.ptr<uint32_t>(ip), g.stream));
+  return st.finish();
 }
 int fp_scale(int field, const uint64_t* a, const uint64_t* k, uint64_t* out, size_t n) {
   if (n == 0) return ZKT_ERR_SHAPE;                                  // assert!(self.len() > 0)
@@ -149,6 +133,30 @@ int tower_batch(int deg, int op, const uint64_t* a, const uint64_t* b, uint64_t*
 }
 
 }  // namespace
+
+// ---- Stage (host_stage.h): the parts that touch the arena, the lock and the error word ----
+Stage::Stage() : lock_(g.mu), stream_(g.stream), small_(g.d_small) {}
+int Stage::commit() {
+  ZCHK(arena_reserve(stage_layout(bytes_, n_, off_)));
+  base_ = g.arena;
+  for (int i = 0; i < n_; ++i)
+    if (src_[i] && bytes_[i]) HIPCHK(hipMemcpyAsync(base_ + off_[i], src_[i], bytes_[i], hipMemcpyHostToDevice, stream_));
+  return ZKT_OK;
+}
+int Stage::downloads() {
+  for (int i = 0; i < n_; ++i)
+    if (dst_[i] && dst_bytes_[i]) HIPCHK(hipMemcpyAsync(dst_[i], base_ + off_[i], dst_bytes_[i], hipMemcpyDeviceToHost, stream_));
+  return ZKT_OK;
+}
+int Stage::finish() {
+  ZCHK(downloads());
+  HIPCHK(hipStreamSynchronize(stream_));
+  return ZKT_OK;
+}
+int Stage::finish_err(int code_if_set) {
+  ZCHK(downloads());
+  return fetch_err(stream_, code_if_set);
+}
 
 int zkt_internal_ready() { return ensure_ready(); }
 hipStream_t zkt_internal_stream() { return g.stream; }
@@ -239,18 +247,11 @@ int zkt_fq12_pow_batch(const uint64_t* a, const uint32_t* e, size_t nl, uint64_t
   if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
   if (n == 0) return ZKT_OK;
   if (!a || !out) return ZKT_ERR_SHAPE;
-  std::lock_guard<std::mutex> lk(g.mu);
-  HIPCHK(hipSetDevice(g.device));
-  int rc = arena_reserve(padded(576 * n) * 2 + padded(nl * 4) + 1024);
-  if (rc) return rc;
-  Carver cv(g.arena);
-  uint32_t* da = cv.take<uint32_t>(576 * n); uint32_t* dout = cv.take<uint32_t>(576 * n); uint32_t* de = cv.take<uint32_t>(nl * 4);
-  HIPCHK(hipMemcpyAsync(da, a, 576 * n, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(de, e, nl * 4, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(launch_fq12_pow(da, de, (int)nl, dout, n, g.stream));
-  HIPCHK(hipMemcpyAsync(out, dout, 576 * n, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return ZKT_OK;
+  Stage st;
+  const int ia = st.in(a, 576 * n), io = st.out(out, 576 * n), ie = st.in(e, nl * 4);
+  ZCHK(st.commit());
+  HIPCHK(launch_fq12_pow(st.ptr<uint32_t>(ia), st.ptr<uint32_t>(ie), (int)nl, st.ptr<uint32_t>(io), n, g.stream));
+  return st.finish();
 }
 
 // diagnostic: the lazy-limb Fq self-test program (fq_program.h) on the device, one run per lane
@@ -258,19 +259,12 @@ int zkt_selftest_fq_program(uint64_t seed0, int steps, const uint64_t* in, uint6
   if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
   if (count == 0) return ZKT_OK;
   if (!in || !out || !violations || steps < 0) return ZKT_ERR_SHAPE;
-  std::lock_guard<std::mutex> lk(g.mu);
-  HIPCHK(hipSetDevice(g.device));
   const size_t eb = 4 * 48;
-  int rc = arena_reserve(padded(eb * count) * 2 + padded(4 * count) + 1024);
-  if (rc) return rc;
-  Carver cv(g.arena);
-  uint32_t* din = cv.take<uint32_t>(eb * count); uint32_t* dout = cv.take<uint32_t>(eb * count); int* dbad = (int*)cv.take<uint32_t>(4 * count);
-  HIPCHK(hipMemcpyAsync(din, in, eb * count, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(launch_selftest_fq_program(seed0, steps, din, dout, dbad, count, g.stream));
-  HIPCHK(hipMemcpyAsync(out, dout, eb * count, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipMemcpyAsync(violations, dbad, 4 * count, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return ZKT_OK;
+  Stage st;
+  const int ii = st.in(in, eb * count), io = st.out(out, eb * count), ib = st.out(violations, 4 * count);
+  ZCHK(st.commit());
+  HIPCHK(launch_selftest_fq_program(seed0, steps, st.ptr<uint32_t>(ii), st.ptr<uint32_t>(io), st.ptr<int>(ib), count, g.stream));
+  return st.finish();
 }
 
 // diagnostic: Fq12 operations of the lane-distributed pairing (zkt_dpairing.hip), same layouts as zkt_fq12_*_batch
@@ -302,23 +296,17 @@ static int group_sum(int grp, const void* pts, size_t n, void* out) {
   if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
   const size_t w = abi_pt_bytes(grp);
   if (!out || (n && !pts)) return ZKT_ERR_SHAPE;
-  if (n == 0) { memset(out, 0, w); ((uint32_t*)out)[w / 4 - 2] = 1; return ZKT_OK; }
-  std::lock_guard<std::mutex> lk(g.mu);
-  HIPCHK(hipSetDevice(g.device));
-  int rc = arena_reserve(padded(w * (n + 1)) + 1024);
-  if (rc) return rc;
-  Carver cv(g.arena);
-  uint32_t* da = cv.take<uint32_t>(w * (n + 1));
-  HIPCHK(hipMemcpyAsync(da, pts, w * n, hipMemcpyHostToDevice, g.stream));
-  if (n == 1) {                                                      // zero + p: goes through the addition so that the coordinates come back reduced
-    std::vector<uint8_t> inf(w, 0); ((uint32_t*)inf.data())[w / 4 - 2] = 1;
-    HIPCHK(hipMemcpyAsync((uint8_t*)da + w, inf.data(), w, hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
+  if (n == 0) { set_infinity(out, w); return ZKT_OK; }
+  alignas(8) uint8_t pair[2 * G2B];                                  // lives until the call's last wait
+  if (n == 1) {                                                      // p + zero: goes through the addition so that the coordinates come back reduced
+    memcpy(pair, pts, w); set_infinity(pair + w, w);
+    pts = pair; n = 2;
   }
-  HIPCHK(launch_group_sum_inplace(grp, da, n == 1 ? 2 : n, g.stream));            // result in da[0]
-  HIPCHK(hipMemcpyAsync(out, da, w, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return ZKT_OK;
+  Stage st;
+  const int ia = st.inout(pts, w * n, out, w);
+  ZCHK(st.commit());
+  HIPCHK(launch_group_sum_inplace(grp, st.ptr<uint32_t>(ia), n, g.stream));       // result in the first point
+  return st.finish();
 }
 static int group_scale(int grp, const void* pts, const uint64_t* k, int limbs, void* out, size_t n) {
   if (limbs < 1 || limbs > 6) return ZKT_ERR_SHAPE;
@@ -452,7 +440,7 @@ static int jac_sum_dev(int grp, const uint32_t* dev_partials, size_t count, void
 static int msm_host(int grp, const void* bases, const uint64_t* scalars, size_t n, void* out) {
   if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
   if (!out || (n && (!bases || !scalars)) || n >= (size_t(1) << 26)) return ZKT_ERR_SHAPE;      // entry offsets are 32-bit: nwin * n < 2^32
-  if (n == 0) { memset(out, 0, abi_pt_bytes(grp)); ((uint32_t*)out)[abi_pt_bytes(grp) / 4 - 2] = 1; return ZKT_OK; }
+  if (n == 0) { set_infinity(out, abi_pt_bytes(grp)); return ZKT_OK; }
   const MsmPlan plan = msm_plan_direct(n, grp);
   const size_t ptb = abi_pt_bytes(grp), cb = grp_coord_bytes(grp);
   const size_t o_abi = 0, o_sc = padded(n * ptb), o_tab = o_sc + padded(n * 32), o_inf = o_tab + padded(n * 2 * cb), o_jac = o_inf + padded(n),
@@ -476,218 +464,6 @@ static int msm_host(int grp, const void* bases, const uint64_t* scalars, size_t 
   return rc;
 }
 
-// ---- SHA-256 and secp256k1 ECDSA (zkt_ecdsa.hip): host-pointer calls staged through the arena on the staging stream ----------------------------------
-namespace {
-// the secp256k1 generator's comb table (built on first use, from a device copy of the generator in g.d_small); caller holds g.mu
-int secp_generator_table(hipStream_t s, const uint32_t** table) {
-  hipError_t e = generator_table(G_SECP, nullptr, table, s);
-  if (e == hipErrorNotReady) {
-    HIPCHK(hipMemcpyAsync(g.d_small, &SECP_GEN, SPB, hipMemcpyHostToDevice, s));
-    e = generator_table(G_SECP, g.d_small, table, s);
-  }
-  HIPCHK(e);
-  return ZKT_OK;
-}
-// bytes of the concatenated messages that the n elements can touch.  As in the BLS calls an element whose end lies before its start is an empty message
-// (the kernels read no byte of it); unlike there, the upload covers the largest offset, so no element reads past it.
-size_t msgs_extent(const uint64_t* offsets, size_t n) {
-  uint64_t m = 0;
-  for (size_t i = 0; i <= n; ++i) m = offsets[i] > m ? offsets[i] : m;
-  return (size_t)m;
-}
-// what one ECDSA call stages: the digests or the messages with their offsets, `a` and `b` (signatures and public keys, or private keys and nonces), the outputs
-struct EcdsaStage { uint8_t *dig = nullptr, *msgs = nullptr; unsigned long long* off = nullptr; uint32_t *a = nullptr, *b = nullptr, *out = nullptr, *flag = nullptr; };
-int ecdsa_stage(const uint8_t* digests, const uint8_t* msgs, const uint64_t* offsets, const void* a, size_t a_bytes, const void* b, size_t b_bytes,
-                size_t out_bytes, size_t n, EcdsaStage& st) {                                      // caller holds g.mu
-  const size_t total = digests ? 0 : msgs_extent(offsets, n);
-  if (total && !msgs) return ZKT_ERR_SHAPE;                      // the extent, not offsets[n]: a non-monotone vector can end at 0 and still name bytes
-  ZCHK(arena_reserve(padded(digests ? n * 32 : total) + padded((n + 1) * 8) + padded(n * a_bytes) + padded(n * b_bytes) + padded(n * out_bytes) + padded(n * 4) + 2048));
-  Carver cv(g.arena);
-  if (digests) { st.dig = cv.take<uint8_t>(n * 32); HIPCHK(hipMemcpyAsync(st.dig, digests, n * 32, hipMemcpyHostToDevice, g.stream)); }
-  else {
-    st.msgs = cv.take<uint8_t>(total); st.off = cv.take<unsigned long long>((n + 1) * 8);
-    if (total) HIPCHK(hipMemcpyAsync(st.msgs, msgs, total, hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipMemcpyAsync(st.off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, g.stream));
-  }
-  st.a = cv.take<uint32_t>(n * a_bytes); st.b = cv.take<uint32_t>(n * b_bytes); st.out = cv.take<uint32_t>(n * out_bytes); st.flag = cv.take<uint32_t>(n * 4);
-  if (a_bytes) HIPCHK(hipMemcpyAsync(st.a, a, n * a_bytes, hipMemcpyHostToDevice, g.stream));
-  if (b_bytes) HIPCHK(hipMemcpyAsync(st.b, b, n * b_bytes, hipMemcpyHostToDevice, g.stream));
-  return ZKT_OK;
-}
-int ecdsa_verify_host(const uint8_t* digests, const uint8_t* msgs, const uint64_t* offsets, const zkt_ecdsa_sig* sigs, const zkt_secp_affine* pks, size_t n, uint32_t* ok) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!sigs || !pks || !ok || (digests ? false : (!offsets || (offsets[n] && !msgs)))) return ZKT_ERR_SHAPE;
-  if (n == 0) return ZKT_OK;
-  std::lock_guard<std::mutex> lk(g.mu);
-  EcdsaStage st; const uint32_t* gtab = nullptr;
-  ZCHK(secp_generator_table(g.stream, &gtab));
-  ZCHK(ecdsa_stage(digests, msgs, offsets, sigs, sizeof(zkt_ecdsa_sig), pks, SPB, 4, n, st));
-  HIPCHK(launch_ecdsa_verify(st.dig, st.msgs, st.off, st.a, st.b, gtab, st.out, n, g.stream));
-  HIPCHK(hipMemcpyAsync(ok, st.out, n * 4, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return ZKT_OK;
-}
-int ecdsa_sign_host(const uint8_t* digests, const uint8_t* msgs, const uint64_t* offsets, const uint64_t* sks, const uint64_t* ks, size_t n, zkt_ecdsa_sig* sigs, uint32_t* retry) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!sks || !ks || !sigs || (digests ? false : (!offsets || (offsets[n] && !msgs)))) return ZKT_ERR_SHAPE;
-  if (n == 0) return ZKT_OK;
-  std::vector<uint32_t> own;                                   // a null `retry` is allowed when no element needs one: the flags are still read back
-  if (!retry) { own.resize(n); }
-  uint32_t* flags = retry ? retry : own.data();
-  std::lock_guard<std::mutex> lk(g.mu);
-  EcdsaStage st; const uint32_t* gtab = nullptr;
-  ZCHK(secp_generator_table(g.stream, &gtab));
-  ZCHK(ecdsa_stage(digests, msgs, offsets, sks, FRB, ks, FRB, sizeof(zkt_ecdsa_sig), n, st));
-  HIPCHK(launch_ecdsa_sign(st.dig, st.msgs, st.off, st.a, st.b, gtab, st.out, st.flag, n, g.stream));
-  HIPCHK(hipMemcpyAsync(sigs, st.out, n * sizeof(zkt_ecdsa_sig), hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipMemcpyAsync(flags, st.flag, n * 4, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  if (!retry) for (size_t i = 0; i < n; ++i) if (flags[i]) { t_err_index = i; return ZKT_ERR_SHAPE; }
-  return ZKT_OK;
-}
-}  // namespace
-int zkt_sha256_batch(const uint8_t* msgs, const uint64_t* offsets, size_t n, uint8_t* digests) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!offsets || !digests || (offsets[n] && !msgs)) return ZKT_ERR_SHAPE;
-  if (n == 0) return ZKT_OK;
-  std::lock_guard<std::mutex> lk(g.mu);
-  EcdsaStage st;
-  ZCHK(ecdsa_stage(nullptr, msgs, offsets, nullptr, 0, nullptr, 0, 32, n, st));
-  HIPCHK(launch_sha256(st.msgs, st.off, n, (uint8_t*)st.out, g.stream));
-  HIPCHK(hipMemcpyAsync(digests, st.out, n * 32, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return ZKT_OK;
-}
-int zkt_ecdsa_public_keys_batch(const uint64_t* sks, size_t n, zkt_secp_affine* pks) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!sks || !pks) return ZKT_ERR_SHAPE;
-  if (n == 0) return ZKT_OK;
-  std::lock_guard<std::mutex> lk(g.mu);
-  ZCHK(arena_reserve(padded(n * FRB) + padded(n * SPB) + 1024));
-  Carver cv(g.arena);
-  uint32_t* dk = cv.take<uint32_t>(n * FRB); uint32_t* dp = cv.take<uint32_t>(n * SPB);
-  HIPCHK(hipMemcpyAsync(dk, sks, n * FRB, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(g.d_small, &SECP_GEN, SPB, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(launch_generator_mul(G_SECP, g.d_small, dk, dp, n, g.stream));                      // any 256-bit sk: (sk mod n) G and sk G are the same group element
-  HIPCHK(hipMemcpyAsync(pks, dp, n * SPB, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return ZKT_OK;
-}
-int zkt_ecdsa_sign_digest_batch(const uint8_t* digests, const uint64_t* sks, const uint64_t* ks, size_t n, zkt_ecdsa_sig* sigs, uint32_t* retry) {
-  if (!digests) return ensure_ready() != ZKT_OK ? ZKT_ERR_DEVICE : ZKT_ERR_SHAPE;
-  return ecdsa_sign_host(digests, nullptr, nullptr, sks, ks, n, sigs, retry);
-}
-int zkt_ecdsa_sign_batch(const uint8_t* msgs, const uint64_t* offsets, const uint64_t* sks, const uint64_t* ks, size_t n, zkt_ecdsa_sig* sigs, uint32_t* retry) {
-  return ecdsa_sign_host(nullptr, msgs, offsets, sks, ks, n, sigs, retry);
-}
-int zkt_ecdsa_verify_digest_batch(const uint8_t* digests, const zkt_ecdsa_sig* sigs, const zkt_secp_affine* pks, size_t n, uint32_t* ok) {
-  if (!digests) return ensure_ready() != ZKT_OK ? ZKT_ERR_DEVICE : ZKT_ERR_SHAPE;
-  return ecdsa_verify_host(digests, nullptr, nullptr, sigs, pks, n, ok);
-}
-int zkt_ecdsa_verify_batch(const uint8_t* msgs, const uint64_t* offsets, const zkt_ecdsa_sig* sigs, const zkt_secp_affine* pks, size_t n, uint32_t* ok) {
-  return ecdsa_verify_host(nullptr, msgs, offsets, sigs, pks, n, ok);
-}
-// device pointers, ordered on the caller's stream: nothing is staged and nothing waits (the first call of a process builds the generator's table on that stream and waits for it)
-int zkt_ecdsa_verify_digest_batch_dev(const uint8_t* dev_digests, const zkt_ecdsa_sig* dev_sigs, const zkt_secp_affine* dev_pks, size_t n, uint32_t* dev_ok, void* stream) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!dev_digests || !dev_sigs || !dev_pks || !dev_ok) return ZKT_ERR_SHAPE;
-  if (n == 0) return ZKT_OK;
-  const uint32_t* gtab = nullptr;
-  { std::lock_guard<std::mutex> lk(g.mu); ZCHK(secp_generator_table((hipStream_t)stream, &gtab)); }
-  HIPCHK(launch_ecdsa_verify(dev_digests, nullptr, nullptr, (const uint32_t*)dev_sigs, (const uint32_t*)dev_pks, gtab, dev_ok, n, (hipStream_t)stream));
-  return ZKT_OK;
-}
-
-// ---- SHA-512 and Ed25519 (zkt_ed25519.hip): bytes in, bytes out, staged like the ECDSA calls --------------------------------------------------------
-namespace {
-// messages (optional) + offsets, then `a` and `b` (n x a_bytes, n x b_bytes: signatures and keys), then n x out_bytes of output.  Caller holds g.mu.
-struct EdStage { uint8_t *msgs = nullptr, *a = nullptr, *b = nullptr, *out = nullptr; unsigned long long* off = nullptr; };
-int ed_stage(const uint8_t* msgs, const uint64_t* offsets, const void* a, size_t a_bytes, const void* b, size_t b_bytes, size_t out_bytes, size_t n, EdStage& st) {
-  const size_t total = offsets ? msgs_extent(offsets, n) : 0;
-  if (total && !msgs) return ZKT_ERR_SHAPE;                      // the extent, not offsets[n]
-  ZCHK(arena_reserve(padded(total) + padded((n + 1) * 8) + padded(n * a_bytes) + padded(n * b_bytes) + padded(n * out_bytes) + 2048));
-  Carver cv(g.arena);
-  if (offsets) {
-    st.msgs = cv.take<uint8_t>(total); st.off = cv.take<unsigned long long>((n + 1) * 8);
-    if (total) HIPCHK(hipMemcpyAsync(st.msgs, msgs, total, hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipMemcpyAsync(st.off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, g.stream));
-  }
-  st.a = cv.take<uint8_t>(n * a_bytes); st.b = cv.take<uint8_t>(n * b_bytes); st.out = cv.take<uint8_t>(n * out_bytes);
-  if (a_bytes) HIPCHK(hipMemcpyAsync(st.a, a, n * a_bytes, hipMemcpyHostToDevice, g.stream));
-  if (b_bytes) HIPCHK(hipMemcpyAsync(st.b, b, n * b_bytes, hipMemcpyHostToDevice, g.stream));
-  return ZKT_OK;
-}
-int ed_finish(void* out, const EdStage& st, size_t bytes) {
-  HIPCHK(hipMemcpyAsync(out, st.out, bytes, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return ZKT_OK;
-}
-}  // namespace
-int zkt_sha512_batch(const uint8_t* msgs, const uint64_t* offsets, size_t n, uint8_t* digests) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!offsets || !digests) return ZKT_ERR_SHAPE;
-  if (n == 0) return ZKT_OK;
-  std::lock_guard<std::mutex> lk(g.mu);
-  EdStage st;
-  ZCHK(ed_stage(msgs, offsets, nullptr, 0, nullptr, 0, 64, n, st));
-  HIPCHK(launch_sha512(st.msgs, st.off, n, st.out, g.stream));
-  return ed_finish(digests, st, n * 64);
-}
-int zkt_ed25519_decode_batch(const uint8_t* enc, size_t n, uint64_t* xy, uint32_t* on_curve) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!enc || !xy || !on_curve) return ZKT_ERR_SHAPE;
-  if (n == 0) return ZKT_OK;
-  std::lock_guard<std::mutex> lk(g.mu);
-  EdStage st;
-  ZCHK(ed_stage(nullptr, nullptr, enc, 32, nullptr, 0, 64 + 4, n, st));
-  uint32_t* dxy = (uint32_t*)st.out; uint32_t* dflag = dxy + n * 16;
-  HIPCHK(launch_ed25519_decode(st.a, n, dxy, dflag, g.stream));
-  HIPCHK(hipMemcpyAsync(on_curve, dflag, n * 4, hipMemcpyDeviceToHost, g.stream));
-  return ed_finish(xy, st, n * 64);
-}
-int zkt_ed25519_public_keys_batch(const uint8_t* prv, size_t n, uint8_t* pub) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!prv || !pub) return ZKT_ERR_SHAPE;
-  if (n == 0) return ZKT_OK;
-  std::lock_guard<std::mutex> lk(g.mu);
-  EdStage st; const uint32_t* btab = nullptr;
-  HIPCHK(ed25519_base_table(&btab, g.stream));
-  ZCHK(ed_stage(nullptr, nullptr, prv, 32, nullptr, 0, 32, n, st));
-  HIPCHK(launch_ed25519_public_keys(st.a, btab, n, st.out, g.stream));
-  return ed_finish(pub, st, n * 32);
-}
-int zkt_ed25519_sign_batch(const uint8_t* msgs, const uint64_t* offsets, const uint8_t* prv, size_t n, uint8_t* sigs) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!offsets || !prv || !sigs) return ZKT_ERR_SHAPE;
-  if (n == 0) return ZKT_OK;
-  std::lock_guard<std::mutex> lk(g.mu);
-  EdStage st; const uint32_t* btab = nullptr;
-  HIPCHK(ed25519_base_table(&btab, g.stream));
-  ZCHK(ed_stage(msgs, offsets, prv, 32, nullptr, 0, 64, n, st));
-  HIPCHK(launch_ed25519_sign(st.msgs, st.off, st.a, btab, n, st.out, g.stream));
-  return ed_finish(sigs, st, n * 64);
-}
-int zkt_ed25519_verify_batch(const uint8_t* msgs, const uint64_t* offsets, const uint8_t* sigs, const uint8_t* pub, size_t n, uint32_t* ok) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!offsets || !sigs || !pub || !ok) return ZKT_ERR_SHAPE;
-  if (n == 0) return ZKT_OK;
-  std::lock_guard<std::mutex> lk(g.mu);
-  EdStage st; const uint32_t* btab = nullptr;
-  HIPCHK(ed25519_base_table(&btab, g.stream));
-  ZCHK(ed_stage(msgs, offsets, sigs, 64, pub, 32, 4, n, st));
-  HIPCHK(launch_ed25519_verify(st.msgs, st.off, st.a, st.b, btab, n, (uint32_t*)st.out, g.stream));
-  return ed_finish(ok, st, n * 4);
-}
-// device pointers, ordered on the caller's stream: nothing is staged and nothing waits (but for the first call of a process, which builds the table of B on that stream)
-int zkt_ed25519_verify_batch_dev(const uint8_t* dev_msgs, const uint64_t* dev_offsets, const uint8_t* dev_sigs, const uint8_t* dev_pub, size_t n, uint32_t* dev_ok, void* stream) {
-  if (ensure_ready() != ZKT_OK) return ZKT_ERR_DEVICE;
-  if (!dev_offsets || !dev_sigs || !dev_pub || !dev_ok) return ZKT_ERR_SHAPE;      // dev_msgs may be NULL when every message is empty: the offsets are on the device, not looked at here
-  if (n == 0) return ZKT_OK;
-  const uint32_t* btab = nullptr;
-  HIPCHK(ed25519_base_table(&btab, (hipStream_t)stream));
-  HIPCHK(launch_ed25519_verify(dev_msgs, (const unsigned long long*)dev_offsets, dev_sigs, dev_pub, btab, n, dev_ok, (hipStream_t)stream));
-  return ZKT_OK;
-}
 
 #define ZKT_MSM_STAGED_API(NAME, GRP, PT)                                                                                       \
   int zkt_##NAME##_jac_sum_dev(const uint32_t* partials, size_t count, void* stream, PT* out) { return jac_sum_dev(GRP, partials, count, stream, out); } \
