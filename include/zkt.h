@@ -494,7 +494,9 @@ int zkt_g1_msm_batch_collect(zkt_g1_bases* bases, zkt_g1_affine* out, uint32_t* 
 int zkt_g1_msm_batch_dev(zkt_g1_bases* bases, const uint64_t* dev_scalars, size_t n, size_t k, size_t vec_stride, void* stream,
                          zkt_g1_affine* out, uint32_t* dev_partials_jac);
 /* combine step of a sharded MSM: sum `count` Jacobian partials (ZKT_G1_PARTIAL_WORDS u32 words each, device)
- * and normalise to affine on the host */
+ * and normalise to affine on the host.  A partial at infinity is a valid operand (the partial of an all-zero scalar vector or of a set of
+ * no bases), and so are equal and opposite partials; a sum at infinity is returned as the point at infinity.  ZKT_ERR_SHAPE, `out`
+ * untouched: count == 0, a null dev_partials or a null out. */
 int zkt_g1_jac_sum_dev(const uint32_t* dev_partials, size_t count, void* stream, zkt_g1_affine* out);
 /* bytes of device workspace a zkt_g1_msm_dev of n terms allocates once and keeps */
 size_t zkt_g1_msm_workspace_bytes(size_t n);
@@ -616,7 +618,9 @@ int zkt_comm_world(void);                                                       
 /* contiguous, balanced index range [lo, hi) of `rank` (the first n % world ranks hold one extra term) */
 void zkt_comm_shard_range(size_t n, int rank, int world, size_t* lo, size_t* hi);
 /* Polynomial::eval_with_g1_hidings (polynomial.rs:271-281) with the terms partitioned over the ranks: `bases` holds THIS rank's shard,
- * dev_scalars its n_local scalars.  Blocking; collective (every rank must call it). */
+ * dev_scalars its n_local scalars.  Blocking; collective (every rank must call it).  n_local == 0 is a valid shard (a handle of
+ * zkt_*_bases_upload(NULL, 0), dev_scalars may be NULL): the rank contributes the point at infinity, as zkt_comm_shard_range gives it when
+ * there are fewer terms than ranks.  A rank whose local stage fails still takes part in the exchange; every rank then returns an error. */
 int zkt_g1_msm_sharded(zkt_g1_bases* bases, const uint64_t* dev_scalars, size_t n_local, void* stream, zkt_g1_affine* out);
 int zkt_g2_msm_sharded(zkt_g2_bases* bases, const uint64_t* dev_scalars, size_t n_local, void* stream, zkt_g2_affine* out);
 int zkt_secp_msm_sharded(zkt_secp_bases* bases, const uint64_t* dev_scalars, size_t n_local, void* stream, zkt_secp_affine* out);

@@ -82,7 +82,8 @@ def stream_functions(header=HEADER):
 
 # ---- symbol -> ("case", id of a case of tests/test_gpu_stream_order.py) | ("exempt", reason) -----------------------------------------
 SHARDED_EXEMPT = ("zkt_comm.cpp:220-224: the call holds the communicator's lock and hands `stream` unchanged to zkt_%s_msm_dev, whose case covers the ordering; "
-                  "the rest is the exchange, which needs a communicator")
+                  "the rest is the exchange and the combine, which need a communicator: tests/test_gpu_combine.py (world 1, and the combine kernel on a caller "
+                  "stream) and tests/comm_cases_worker.py (worlds 3 and 8) run them against python integers")
 TABLE = {
     "zkt_fq_mul_batch_dev": ("case", "fq_mul_batch_dev"),
     "zkt_g1_mul_batch_dev": ("case", "g1_mul_batch_dev"),

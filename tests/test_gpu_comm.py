@@ -152,3 +152,37 @@ def test_comm_world2_callback_transport_two_processes_one_card():
         outs.append(out)
     for rank, (p, out) in enumerate(zip(procs, outs)):
         assert p.returncode == 0 and f"COMM_WORKER_OK {rank}" in out, f"rank {rank} rc={p.returncode}\n{out[-3000:]}"
+
+
+def _run_comm_cases(world, port):
+    """`world` ranks of tests/comm_cases_worker.py on this one card (with this process: world + 1 <= 9 processes on the GPU): every rank must report COMM_CASES_OK.
+    A rank that hangs is killed with all the others when the limit runs out."""
+    import time
+    t0 = time.time()
+    procs = []
+    for rank in range(world):
+        env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+        procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, "comm_cases_worker.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+    outs = []
+    for p in procs:
+        try:
+            out, _ = p.communicate(timeout=420)
+        except subprocess.TimeoutExpired:
+            for q in procs: q.kill()
+            raise
+        outs.append(out)
+    print(f"comm cases, world {world}: {time.time() - t0:.1f} s")
+    for rank, (p, out) in enumerate(zip(procs, outs)):
+        assert p.returncode == 0 and f"COMM_CASES_OK {rank}" in out, f"rank {rank} rc={p.returncode}\n{out[-4000:]}"
+
+
+def test_comm_world3_exceptional_shards_three_processes_one_card():
+    """odd world: an empty last shard, an uneven split, one doubling and one generic addition in the combine, a left-over point beside a cancelling pair,
+    a failing rank, a failing callback, sharded Groth16 proofs of 3 and 200 constraints (tests/comm_cases_worker.py)"""
+    _run_comm_cases(3, 30100 + (os.getpid() % 200))
+
+
+def test_comm_world8_exceptional_shards_eight_processes_one_card():
+    """the benchmark's world: eight receive slots, every tree addition of the combine a doubling (same point on every rank), a sum that cancels to infinity,
+    a Groth16 proof with one constraint per rank (tests/comm_cases_worker.py)"""
+    _run_comm_cases(8, 30400 + (os.getpid() % 200))
